@@ -56,6 +56,10 @@ WORKLOADS = {
 }
 CFG5_CROP = 1024          # crop side (cells) of the cfg5 workload's TopdownMap.select leg
 ROT_TARGET_BYTES = 600 << 20      # rotate until a step's buffers come around after > 2 x 256 MiB
+DUMP_FULL_MAX = 1 << 20           # --dump-outputs: an output of up to this many elements is written whole,
+DUMP_SAMPLE = 1 << 19             # a larger one as this many elements at seeded positions
+DUMP_SEED = 0
+DUMP_MASKS = {"top": "mask", "fused": "fused_mask", "crop": "crop_mask"}   # map -> its mask (map != fill)
 
 
 def algorithmic_bytes(B, H, W, mh, mw, C, fused_only=False):
@@ -66,6 +70,33 @@ def algorithmic_bytes(B, H, W, mh, mw, C, fused_only=False):
   if C == 0:
     return depth + B * mh * mw * (4 + 1)
   return depth + B * C * H * W * 4 + B * C * mh * mw * (4 + 1)     # object map, no height map
+
+
+def dump_outputs(out_dir, arrays):
+  """--dump-outputs: every named output as OUT_DIR/<name>.npy, float32 (masks as 0 / 1).  An output
+  of more than DUMP_FULL_MAX elements is written as DUMP_SAMPLE elements at sorted flat positions
+  drawn from a generator seeded with DUMP_SEED (the same positions for every output of that size),
+  the positions beside it as OUT_DIR/<name>_index.npy (float64).  A map's cells outside its mask
+  (DUMP_MASKS) hold the fill value, -inf for height maps, and are written as 0: every value written
+  is finite, so that two dumps compare with ordinary tolerances.  At most 64 MB in all."""
+  files = {}
+  for name, t in arrays.items():
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_FULL_MAX:      # (a map and its mask have one size: the same positions)
+      idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+      files[name] = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+      files[name + "_index"] = idx.astype(np.float64)
+    else:
+      files[name] = t.detach().float().cpu().numpy()
+  for name, m in DUMP_MASKS.items():
+    if name in files:
+      files[name] = np.where(files[m] != 0, files[name], np.float32(0))
+  total = sum(a.nbytes for a in files.values())
+  assert total <= 64_000_000, f"--dump-outputs: {total} bytes"
+  os.makedirs(out_dir, exist_ok=True)
+  for f, a in files.items():
+    assert np.isfinite(a).all(), f"--dump-outputs: {f} has non-finite values"
+    np.save(os.path.join(out_dir, f + ".npy"), a)
 
 
 def synthetic_inputs(B, H, W, C, seed, device, scene):
@@ -118,6 +149,9 @@ def main():
                   help="depth batches / output sets the steps rotate over (0: as many as it takes for a "
                        "step's buffers to come around after more than twice the Infinity Cache; 1: one "
                        "set, everything cache resident -- rounds 1-3 measured that)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step computed (rank 0's outputs) to DIR/<name>.npy, "
+                       "float32; outputs of more than 2**20 elements as a fixed seeded sample")
   args = ap.parse_args()
 
   world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -284,6 +318,8 @@ def main():
       top, mask, grid = proj.orth_project_and_flow(depth_d, flow_tp, cam_pose=pose, out=out_sets[n % rot])
       crop, crop_mask = dmap.functional.crop_nearest(top, centers[n % len(pose_sets)], CFG5_CROP, CFG5_CROP,
                                                      fill_value=fill, mask=mask)
+      if args.dump_outputs:      # the call's other results, kept until the next step for --dump-outputs
+        state["extras"] = {"grid": grid, "crop": crop, "crop_mask": crop_mask}
       del grid, crop, crop_mask
       return top, mask, top[0], mask[0]
     # per-frame maps + masks and this rank's partial global map, one launch sequence
@@ -338,6 +374,19 @@ def main():
 
   trace = [] if os.environ.get("DM_BENCH_TRACE") else None
   elapsed, enqueue_s, rank_ms, out, new_segments, t0 = timed_run(args.steps, args.warmup, RING_MAX, trace)
+  if args.dump_outputs and rank == 0:
+    # the last timed step's results as its caller holds them (N > 1: the all-reduced map and its
+    # mask), copied out before the measurements below write into the rotating output sets again
+    if cfg5:
+      outputs = {"top": out[0], "mask": out[1], **state["extras"]}
+    else:
+      fused_mask = out[3] if dist is None else dmap.mask_from_map(out[2], fill)
+      outputs = {"fused": out[2], "fused_mask": fused_mask}
+      if not fused_only:
+        outputs = {"top": out[0], "mask": out[1], **outputs}
+    dump_outputs(args.dump_outputs, outputs)
+    del outputs
+    state.pop("extras", None)
 
   # checksum of the last step's fused map (a one-rank RCCL run must reproduce the plain run), taken
   # before the measurements below write into the rotating output sets again

@@ -219,7 +219,7 @@ def _bench(args, launcher):
   return json.loads(lines[0])
 
 
-def test_bench_rccl_leg_with_one_rank():
+def test_bench_rccl_leg_with_one_rank(tmp_path):
   """bench.py launched the way the driver launches N > 1 (torch.distributed.run), with one
   rank: `nccl` process group on real RCCL, the ring of partial maps, all_reduce(MAX),
   mask_from_map -- and the fused map must equal the single-process one (checksums of the
@@ -229,15 +229,51 @@ def test_bench_rccl_leg_with_one_rank():
     pytest.skip("needs a GPU")
   common = ["--gpus", "1", "--steps", "40", "--warmup", "4", "--no-cpu-baseline", "--no-other-configs"]
   port = 29650 + os.getpid() % 300
-  one = _bench(common, ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-                        "--master-addr", "127.0.0.1", "--master-port", str(port)])
-  solo = _bench(common, [])
+  one = _bench(common + ["--dump-outputs", str(tmp_path / "one")],
+               ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
+                "--master-addr", "127.0.0.1", "--master-port", str(port)])
+  solo = _bench(common + ["--dump-outputs", str(tmp_path / "solo")], [])
   for r in (one, solo):
     assert r["n_gpus"] == 1 and r["steps"] == 40 and r["value"] > 0
     assert r["roofline"]["frac"] > 0 and r["unit"] == "frames/s"
   assert "RCCL" in one["config"]["parallelism"]
   assert one["fused_checksum"] == solo["fused_checksum"]
   assert one["fused_checksum"]["cells"] > 0
+  a, b = _dumped(tmp_path / "one"), _dumped(tmp_path / "solo")
+  assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def _dumped(d):
+  return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_bench_dump_outputs(tmp_path):
+  """bench.py --dump-outputs DIR: the last timed step's per-frame maps and masks (a seeded sample) and its
+  fused map and mask (whole) as float32 .npy, finite (cells off a map's mask as 0), at most 64 MB; the
+  fused map is the one the JSON line's checksum describes, and a second run with the same arguments writes the same arrays."""
+  if not torch.cuda.is_available():
+    pytest.skip("needs a GPU")
+  common = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-other-configs",
+            "--no-two-streams"]
+  r = _bench(common + ["--dump-outputs", str(tmp_path / "a")], [])
+  _bench(common + ["--dump-outputs", str(tmp_path / "b")], [])
+  assert r["steps"] == 3 and r["warmup"] == 2
+  a, b = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+  assert set(a) == {"top", "top_index", "mask", "mask_index", "fused", "fused_mask"}
+  assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000
+  assert a["fused"].shape == a["fused_mask"].shape == (1, 512, 512)
+  assert a["top"].shape == a["mask"].shape == (1 << 19,)
+  assert np.array_equal(a["top_index"], a["mask_index"]) and a["top_index"].dtype == np.float64
+  assert np.all(np.diff(a["top_index"]) > 0) and a["top_index"][-1] < 64 * 512 * 512
+  for k in ("top", "mask", "fused", "fused_mask"):
+    assert a[k].dtype == np.float32 and np.isfinite(a[k]).all()
+  for m, k in (("mask", "top"), ("fused_mask", "fused")):
+    assert np.isin(a[m], (0, 1)).all() and a[m].any() and not a[m].all()
+    assert not a[k][a[m] == 0].any()          # the fill (-inf) cells, written as 0
+  fm = a["fused_mask"] == 1
+  assert int(fm.sum()) == r["fused_checksum"]["cells"] > 0
+  assert np.isclose(a["fused"][fm].astype(np.float64).sum(), r["fused_checksum"]["sum"], rtol=1e-9, atol=1e-6)
+  assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_the_drivers_bench_command_has_no_stall(oracle):
