@@ -368,6 +368,69 @@ int dm_camera_affine_grid_f32(const dm_params* p, const dm_frame* frames, const 
   return DM_OK;
 }
 
+// Arguments both backward entry points share; every refusal happens before any HIP call.
+static int check_backward(const dm_params* p, const dm_frame* frames, const float* depth_dev,
+                          const void* workspace_dev, size_t workspace_bytes) {
+  int rc = check_params(p);
+  if (rc != DM_OK) return rc;
+  if (p->reduction == DM_REDUCE_PROD)
+    return fail(DM_ERR_UNSUPPORTED, "orth_project has no backward for reduction 'prod'");
+  if (p->B == 0) return DM_OK;
+  if (!frames || !depth_dev) return fail(DM_ERR_INVALID_ARGUMENT, "frames/depth must not be NULL");
+  if (!workspace_dev || workspace_bytes < (size_t)p->B * sizeof(dm_frame))
+    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes,
+                (size_t)p->B * sizeof(dm_frame));
+  return DM_OK;
+}
+
+int dm_orth_project_winners_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
+                                const float* value_dev, const uint8_t* valid_dev, const float* out_dev,
+                                const float* height_dev, int32_t* winner_dev, int32_t* height_winner_dev,
+                                void* workspace_dev, size_t workspace_bytes, void* stream) {
+  int rc = check_backward(p, frames, depth_dev, workspace_dev, workspace_bytes);
+  if (rc != DM_OK) return rc;
+  if ((p->vc > 0) != (value_dev != nullptr))
+    return fail(DM_ERR_INVALID_ARGUMENT, "value pointer and vc=%d disagree", p->vc);
+  if ((p->valid_c > 0) != (valid_dev != nullptr))
+    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
+  if (winner_dev && p->reduction == DM_REDUCE_SUM)
+    return fail(DM_ERR_INVALID_ARGUMENT, "reduction 'sum' has no winners or counts");
+  if (winner_dev && p->reduction != DM_REDUCE_MEAN && !out_dev)
+    return fail(DM_ERR_INVALID_ARGUMENT, "max / min winners need the forward's output");
+  if (height_winner_dev && (!p->vc || !height_dev))
+    return fail(DM_ERR_INVALID_ARGUMENT, "height winners need a value map (vc > 0) and its height map");
+  if (p->B == 0 || (!winner_dev && !height_winner_dev)) return DM_OK;
+  hipError_t e = dm::run_winners(*p, frames, depth_dev, value_dev, valid_dev, out_dev, height_dev,
+                                 winner_dev, height_winner_dev, workspace_dev,
+                                 static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
+  return DM_OK;
+}
+
+int dm_orth_project_backward_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
+                                 const uint8_t* valid_dev, const int32_t* winner_dev,
+                                 const int32_t* height_winner_dev, const float* grad_out_dev,
+                                 const float* grad_height_dev, float* grad_value_dev,
+                                 float* grad_depth_dev, double* moments_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream) {
+  int rc = check_backward(p, frames, depth_dev, workspace_dev, workspace_bytes);
+  if (rc != DM_OK) return rc;
+  if ((p->valid_c > 0) != (valid_dev != nullptr))
+    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
+  if (grad_out_dev && p->reduction != DM_REDUCE_SUM && !winner_dev)
+    return fail(DM_ERR_INVALID_ARGUMENT, "reduction %d needs the winners / counts", p->reduction);
+  if (grad_value_dev && !p->vc)
+    return fail(DM_ERR_INVALID_ARGUMENT, "grad_value needs a value map (vc > 0)");
+  if (grad_height_dev && (!p->vc || !height_winner_dev))
+    return fail(DM_ERR_INVALID_ARGUMENT, "grad_height needs a value map (vc > 0) and the height winners");
+  if (p->B == 0 || (!grad_value_dev && !grad_depth_dev && !moments_dev)) return DM_OK;
+  hipError_t e = dm::run_backward(*p, frames, depth_dev, valid_dev, winner_dev, height_winner_dev,
+                                  grad_out_dev, grad_height_dev, grad_value_dev, grad_depth_dev,
+                                  moments_dev, workspace_dev, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
+  return DM_OK;
+}
+
 static int check_fuse_src(const dm_fuse_src* s) {
   if (!s) return fail(DM_ERR_INVALID_ARGUMENT, "src is NULL");
   if (s->b < 0 || s->b > DM_FUSE_MAX_BATCH || s->c < 0 || s->c > 65535 || s->h < 1 || s->w < 1 ||

@@ -88,4 +88,13 @@ hipError_t run_scatter(const float* values, const long long* index, float* canva
                        int R, int C, int Ci, size_t N, size_t M, float fill, int has_fill,
                        int reduction, void* ws, hipStream_t s);
 
+// dm_backward.hip -- backward of orth_project: winners / counts, then per-pixel gradients
+hipError_t run_winners(const dm_params& p, const dm_frame* frames_host, const float* depth,
+                       const float* value, const uint8_t* valid, const float* out,
+                       const float* height, int32_t* win, int32_t* hwin, void* ws, hipStream_t s);
+hipError_t run_backward(const dm_params& p, const dm_frame* frames_host, const float* depth,
+                        const uint8_t* valid, const int32_t* win, const int32_t* hwin,
+                        const float* grad_out, const float* grad_height, float* grad_value,
+                        float* grad_depth, double* moments, void* ws, hipStream_t s);
+
 }  // namespace dm

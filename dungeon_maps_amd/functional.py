@@ -250,11 +250,175 @@ def orth_project(
   unproject, pitch/yaw/translate, truncations, quantisation, scatter-reduce and
   the changed-mask (dm_orth_project_f32).
   """
+  if torch.is_grad_enabled() and _wants_grad(depth_map, value_map, cam_pitch, cam_height) \
+      and Reduction(reduction) is not Reduction.prod:
+    return _orth_project_grad(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
+                              cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
+                              center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
+                              clip_border, to_global, flip_h, fill_value, reduction, get_height_map,
+                              device)
   return _orth_project(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
                        cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
                        center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
                        clip_border, to_global, flip_h, fill_value, reduction, get_height_map,
                        device, False, None, None)
+
+
+# ---------------------------------------------------------------------------
+# Autograd of orth_project (the reference's chain rule: unproject -> rotations -> torch_scatter's
+# backward, cells cut from the graph).  Taken only when grad mode is on and depth_map, value_map,
+# cam_height or cam_pitch requires grad; every other call goes the route above unchanged.
+# The forward is dm_orth_project_f32 itself (outputs bit-identical to the no-grad call); the
+# winners / counts the backward needs are computed lazily in .backward()
+# (dm_orth_project_winners_f32, then dm_orth_project_backward_f32).  Reduction 'prod' has no
+# backward: its outputs keep no grad_fn, as the other entry points' (orth_project_and_fuse,
+# orth_project_fused, orth_project_and_flow, PreparedProjection, project / scatter_nd).
+# ---------------------------------------------------------------------------
+def _wants_grad(*xs) -> bool:
+  return any(torch.is_tensor(x) and x.requires_grad for x in xs)
+
+
+_ANGLE_EPS = np.float32(0.001)   # reference utils.py:47, the rotation's |angle| clamp
+
+
+def _frame_column(x, batch: int, device) -> Optional[torch.Tensor]:
+  """A per-frame argument that requires grad as a differentiable float32 (batch,) tensor
+  (1 or batch rows, like frames.build_frame_table reads it); None otherwise."""
+  if not (torch.is_tensor(x) and x.requires_grad):
+    return None
+  t = x.to(device=device, dtype=torch.float32).reshape(-1)
+  if t.numel() == 1 and batch != 1:
+    t = t.expand(batch)
+  if t.numel() != batch:
+    raise ValueError(f"per-frame argument has {t.numel()} rows, expected 1 or {batch}")
+  return t
+
+
+class _OrthProjectFn(torch.autograd.Function):
+  """(depth, value, pitch, cam_height) -> (topdown, mask[, height (B, dc, mh, mw)])."""
+
+  @staticmethod
+  def forward(ctx, call, get_height, depth, value, pitch, cam_h):
+    p = call.params
+    shape = (p.B, call.oc, p.mh, p.mw)
+    topdown = torch.empty(shape, dtype=torch.float32, device=call.dev)
+    mask = torch.empty(shape, dtype=torch.bool, device=call.dev)
+    height = None
+    if get_height and p.vc:
+      height = torch.empty((p.B, p.dc, p.mh, p.mw), dtype=torch.float32, device=call.dev)
+    ws, ws_bytes = call.workspace()
+    _native.check_status()
+    with _on_device(call.dev):
+      _native.check(_native.lib().dm_orth_project_f32(
+          ctypes.byref(p), _ptr(call.frames), _ptr(depth), _ptr(value), _ptr(call.valid),
+          _ptr(topdown), _ptr(mask), _ptr(height), None, None, _ptr(ws), ws_bytes,
+          _native.status_ptr(), _stream_ptr(call.dev)))
+    ctx.call = call
+    ctx.pitch = None if pitch is None else pitch.detach()
+    ctx.mark_non_differentiable(mask)
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(depth, value, call.valid, topdown, height)
+    if height is None:
+      return topdown, mask
+    return topdown, mask, height
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, grad_top, _grad_mask, grad_height=None):
+    call = ctx.call
+    p = call.params
+    depth, value, valid, topdown, height = ctx.saved_tensors
+    need_depth, need_value, need_pitch, need_h = ctx.needs_input_grad[2:6]
+    need_w = need_depth or need_pitch or need_h         # the heights' gradient w is wanted
+    dev, B, M = call.dev, p.B, (p.mh, p.mw)
+    i32 = dict(dtype=torch.int32, device=dev)
+    g_top = None if grad_top is None else grad_top.to(torch.float32).contiguous()
+    g_h = None
+    if grad_height is not None and p.vc and need_w:
+      g_h = grad_height.to(torch.float32).contiguous()
+    win = hwin = None
+    if g_top is not None and (need_value if p.vc else need_w):
+      if p.reduction in (_native.REDUCE_MAX, _native.REDUCE_MIN):
+        win = torch.empty((B, call.oc) + M, **i32)
+      elif p.reduction == _native.REDUCE_MEAN:
+        win = torch.empty((B, p.dc) + M, **i32)
+    if not p.vc and need_w and g_top is None:
+      need_w = False
+    if g_h is not None:
+      hwin = torch.empty((B, p.dc) + M, **i32)
+    if p.vc and g_h is None:
+      need_w = False
+    g_value = torch.empty_like(value) if (need_value and g_top is not None) else None
+    g_depth = torch.empty_like(depth) if (need_depth and need_w) else None
+    moments = torch.empty((B, 4), dtype=torch.float64, device=dev) \
+        if (need_w and (need_pitch or need_h)) else None
+    ws_bytes = B * _native.FRAME_FLOATS * 4
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib, stream = _native.lib(), _stream_ptr(dev)
+    with _on_device(dev):
+      if win is not None or hwin is not None:
+        _native.check(lib.dm_orth_project_winners_f32(
+            ctypes.byref(p), _ptr(call.frames), _ptr(depth), _ptr(value), _ptr(valid),
+            _ptr(topdown), _ptr(height), _ptr(win), _ptr(hwin), _ptr(ws), ws_bytes, stream))
+      if g_value is not None or g_depth is not None or moments is not None:
+        _native.check(lib.dm_orth_project_backward_f32(
+            ctypes.byref(p), _ptr(call.frames), _ptr(depth), _ptr(valid), _ptr(win), _ptr(hwin),
+            _ptr(g_top if (win is not None or p.reduction == _native.REDUCE_SUM) else None),
+            _ptr(g_h), _ptr(g_value), _ptr(g_depth), _ptr(moments), _ptr(ws), ws_bytes, stream))
+    if need_value and g_value is None:
+      g_value = torch.zeros_like(value)
+    if need_depth and g_depth is None:
+      g_depth = torch.zeros_like(depth)
+    g_pitch = g_camh = None
+    if need_pitch or need_h:
+      g_pitch, g_camh = _camera_grads(moments, ctx.pitch, B, dev, need_pitch, need_h)
+    return (None, None, g_depth if need_depth else None, g_value if need_value else None,
+            g_pitch, g_camh)
+
+
+def _camera_grads(moments, pitch, B, dev, need_pitch, need_h):
+  """d loss / d cam_pitch and d cam_height (float32, (B,)) from the per-frame moments
+  (sum w, w*X, w*Y, w*z) of the heights' gradient w.  y2 = Ry_row1 . (Rp^T (X, Y, z) + (0, h, 0))
+  with Ry a rotation about Y (row 1 = (0, 1, 0), the identity's without to_global) and
+  Rp = rotate([1,0,0], a): rows 1, 4, 7 of the frame table are 0, 1 - (1 - cos a), sin a
+  (reference utils.py:303-327), so dy2/dh = 1 and dy2/da = -sin(a) Y + cos(a) z, and 0 where the
+  rotation clamps |a| <= 1e-3 to 0."""
+  if moments is None:
+    z = torch.zeros(B, dtype=torch.float32, device=dev)
+    return (z if need_pitch else None), (z.clone() if need_h else None)
+  g_h = moments[:, 0].to(torch.float32) if need_h else None
+  g_p = None
+  if need_pitch:
+    a = pitch.to(torch.float64)
+    g = torch.cos(a) * moments[:, 3] - torch.sin(a) * moments[:, 2]
+    g_p = torch.where(pitch.abs() > _ANGLE_EPS.item(), g, torch.zeros_like(g)).to(torch.float32)
+  return g_p, g_h
+
+
+def _orth_project_grad(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
+                       cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
+                       center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
+                       clip_border, to_global, flip_h, fill_value, reduction, get_height_map, device):
+  """orth_project through _OrthProjectFn.  The dtype / device / layout conversions happen in
+  _Call with torch ops (autograd sees them); so does the copy back to a CPU target."""
+  call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
+               cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
+               center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
+               clip_border, to_global, flip_h, fill_value, reduction, device)
+  B = call.params.B
+  pitch = _frame_column(cam_pitch, B, call.dev)
+  cam_h = _frame_column(cam_height, B, call.dev)
+  outs = _OrthProjectFn.apply(call, bool(get_height_map), call.depth, call.value, pitch, cam_h)
+  topdown, mask = outs[0], outs[1]
+  height = outs[2] if len(outs) > 2 else None
+  if call.target != call.dev:
+    topdown, mask = topdown.to(call.target), mask.to(call.target)
+    height = None if height is None else height.to(call.target)
+  if not get_height_map:
+    return topdown, mask
+  if height is None:
+    return topdown, mask, topdown
+  return topdown, mask, torch.broadcast_to(height, topdown.shape)
 
 
 def _orth_project(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,

@@ -301,7 +301,11 @@ def crop_topdown_map(source: TopdownMap, center, crop_width: int, crop_height: i
   dev = source.height_map.device
   woff = utils.to_tensor(proj.width_offset, device=center.device)
   hoff = utils.to_tensor(proj.height_offset, device=center.device)
-  if dev.type == "cuda" and mode in F.SAMPLE_MODES:
+  # a source map that requires grad (orth_project's autograd path) is cropped by the differentiable
+  # torch route below, as in the reference ("Differentiable crop top-down map", maps.py:1968)
+  wants_grad = torch.is_grad_enabled() and (
+      source.height_map.requires_grad or (not source.is_height_map and source.topdown_map.requires_grad))
+  if dev.type == "cuda" and mode in F.SAMPLE_MODES and not wants_grad:
     # one fused HIP kernel per image instead of pad + grid + grid_sample (nearest: a gather; bilinear / bicubic:
     # torch's grid_sample arithmetic, dm_crop_sample_f32)
     height_map, mask = F.crop_sample(source.height_map, center, crop_width, crop_height,

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 10
+#define DM_ABI_VERSION 11
 
 typedef enum dm_status {
   DM_OK = 0,
@@ -196,6 +196,45 @@ int dm_orth_project_flow_f32(const dm_params* p, const dm_frame* frames, const d
                              uint8_t* mask_dev, float* fused_dev, uint8_t* fused_mask_dev,
                              float* grid_dev, void* workspace_dev, size_t workspace_bytes,
                              int32_t* status_dev, void* stream);
+
+/*
+ * Backward of dm_orth_project_f32 (autograd of the reference's chain: unproject -> rotations ->
+ * torch_scatter's backward; cells are cut from the graph).  Two calls with the arguments of the
+ * forward (p, the host frame table, depth / value / valid) and its results; reduction 'prod' has
+ * no backward (DM_ERR_UNSUPPORTED).  The workspace needs B * sizeof(dm_frame) bytes.  Every
+ * argument error is reported before any HIP call.
+ *
+ * dm_orth_project_winners_f32: what the gradient of each cell needs.
+ *   winner_dev         max / min: (B, oc, mh, mw) int32, the lowest flat pixel index h*W+w whose
+ *                      value equals out_dev's cell while the cell's changed-mask is set
+ *                      (torch_scatter's CPU argmax: strict '>' in index order), -1 when no pixel
+ *                      won.  mean: (B, dc, mh, mw) int32 counts of the valid in-bounds pixels.
+ *                      sum: must be NULL.  NULL: not computed.
+ *   height_winner_dev  with a value map (vc > 0) and the forward's height_dev: (B, dc, mh, mw)
+ *                      int32 winners of the NINF / max height map.  NULL: not computed.
+ * dm_orth_project_backward_f32: per pixel, weight of its cell (winner 1 / other 0, sum 1,
+ * mean 1 / count) times the incoming gradient.
+ *   grad_out_dev     (B, oc, mh, mw) gradient of out_dev, or NULL (zero)
+ *   grad_height_dev  (B, dc, mh, mw) gradient of height_dev (vc > 0 only), or NULL (zero)
+ *   grad_value_dev   (B, vc, H, W) out, or NULL
+ *   grad_depth_dev   (B, dc, H, W) out, or NULL: w * d(height)/d(depth), w the gradient of the
+ *                    pixel's height (from grad_out_dev without a value map, from
+ *                    grad_height_dev with one)
+ *   moments_dev      (B, 4) float64 out, or NULL: per frame sum w, sum w*X, sum w*Y, sum w*z over
+ *                    all depth channels, (X, Y, z) the pixel in camera space -- the caller chains
+ *                    them through d(Rp)/d(pitch) and d(height)/d(cam_height).  Accumulated with
+ *                    atomics: the summation order (last bits) varies from run to run.
+ */
+int dm_orth_project_winners_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
+                                const float* value_dev, const uint8_t* valid_dev, const float* out_dev,
+                                const float* height_dev, int32_t* winner_dev, int32_t* height_winner_dev,
+                                void* workspace_dev, size_t workspace_bytes, void* stream);
+int dm_orth_project_backward_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
+                                 const uint8_t* valid_dev, const int32_t* winner_dev,
+                                 const int32_t* height_winner_dev, const float* grad_out_dev,
+                                 const float* grad_height_dev, float* grad_value_dev,
+                                 float* grad_depth_dev, double* moments_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream);
 
 /*
  * camera_affine_grid (maps.py:353-460): per pixel of depth (B, dc, H, W) the
