@@ -21,7 +21,13 @@ for fixed random weights; saved: the gradients with respect to depth, value, cam
 cam_height, with the inputs, weights, the forward outputs and the configuration.  The .npz is
 written with fixed zip timestamps, so a rerun reproduces it byte for byte.
 
-Usage:  python tests/golden/gen_golden_grad.py   (writes tests/golden/g14_orth_project_grad.npz)
+g15 (CASES_G15) covers what g14's cases leave out, with per-case options: a loss on the height map
+alone (no topdown term: ``loss_top`` is saved as 0), one 0-d cam_height shared by both frames (the
+frames' gradients summed, saved 0-d) and pitches set exactly in float32 (the |a| <= 1e-3 clamp's
+edge).
+
+Usage:  python tests/golden/gen_golden_grad.py
+        (writes tests/golden/g14_orth_project_grad.npz and tests/golden/g15_orth_project_grad.npz)
 """
 import io
 import os
@@ -37,6 +43,7 @@ sys.path.insert(0, HERE)
 import gen_golden as gg  # noqa: E402  (scene_depth, T, the reference's location)
 
 NAME = "g14_orth_project_grad"
+NAME_G15 = "g15_orth_project_grad"
 
 
 class _ScatterArg(torch.autograd.Function):
@@ -137,6 +144,25 @@ CASES = [
     ("max_pitch_clamp", "max", None, "none", 0, 1, False, None, (0.15, 5.05, None), True, True, False,
      (float(np.degrees(0.0005)), -20.)),
 ]
+_EPS32 = np.float32(0.001)
+# as CASES, plus options: loss_top (False: the loss has no topdown term), shared_height (one 0-d
+# cam_height for both frames), pitch (float32 radians, replacing the pitches' values; the scenes
+# still use the pitches in degrees)
+CASES_G15 = [
+    ("max_height_dc3", "max", -np.inf, "none", 0, 3, True, None, (0.15, 5.05, None), True, True, False,
+     (-20., -15.), {}),
+    ("min_cont_local_height", "min", None, "cont", 3, 1, True, None, (0.15, 5.05, None), False, True, True,
+     (-20., -25.), {}),
+    ("max_height_fill_in_range", "max", 0.002, "none", 0, 1, False, None, (0.15, 5.05, None), True, True, False,
+     (-20., -18.), {}),
+    ("height_only_loss_onehot", "max", None, "onehot", 4, 1, True, None, (0.15, 5.05, None), True, True, True,
+     (-20., -22.), {"loss_top": False}),
+    ("max_onehot_shared_cam_height", "max", None, "onehot", 3, 1, False, None, (0.15, 5.05, None), True, False,
+     True, (-20., -20.), {"shared_height": True}),
+    ("max_pitch_at_eps", "max", None, "none", 0, 1, False, None, (0.15, 5.05, None), True, True, False,
+     (float(np.degrees(0.001)), float(np.degrees(0.001))),
+     {"pitch": np.array([_EPS32, np.nextafter(_EPS32, np.float32(1))], dtype=np.float32)}),
+]
 POSES = np.array([[0.2, 0.1, -0.3], [-0.4, 0.3, 0.7]], dtype=np.float32)
 CAM_H = np.array([0.88, 1.05], dtype=np.float32)
 
@@ -158,15 +184,24 @@ def _case_inputs(rng, vkind, vc, dc, use_valid, pitches):
 
 def run_case(dmap, rng, case):
   (name, red, fill, vkind, vc, dc, use_valid, clip, (dmin, dmax, hmax), to_global, flip_h,
-   get_height, pitches) = case
+   get_height, pitches) = case[:13]
+  opts = case[13] if len(case) > 13 else None
   depth, value, valid = _case_inputs(rng, vkind, vc, dc, use_valid, pitches)
   B = depth.shape[0]
   oc = vc if vc else dc
   weights = rng.normal(size=(B, oc, 32, 32)).astype(np.float32)
   hweights = rng.normal(size=(B, oc, 32, 32)).astype(np.float32)
   pitch = np.radians(np.asarray(pitches, dtype=np.float64)).astype(np.float32)
+  loss_top, shared_h, cam_h = True, False, CAM_H[:B].copy()
+  if opts is not None:
+    loss_top, shared_h = opts.get("loss_top", True), opts.get("shared_height", False)
+    pitch = opts.get("pitch", pitch)
+    if shared_h:
+      cam_h = np.full(B, CAM_H[0], dtype=np.float32)
   out = {f"{name}/depth": depth, f"{name}/weights": weights, f"{name}/pitch": pitch,
-         f"{name}/cam_height": CAM_H[:B].copy(), f"{name}/cam_pose": POSES[:B].copy()}
+         f"{name}/cam_height": cam_h[0].copy() if shared_h else cam_h, f"{name}/cam_pose": POSES[:B].copy()}
+  if opts is not None:
+    out[f"{name}/loss_top"] = np.asarray(int(loss_top))
   if value is not None:
     out[f"{name}/value"] = value
   if valid is not None:
@@ -182,10 +217,10 @@ def run_case(dmap, rng, case):
     v = None if value is None else torch.tensor(value[b:b + 1]).requires_grad_()
     m = None if valid is None else torch.tensor(valid[b:b + 1])
     p = torch.tensor(pitch[b:b + 1]).requires_grad_()
-    h = torch.tensor(CAM_H[b:b + 1]).requires_grad_()
+    h = torch.tensor(cam_h[b:b + 1]).requires_grad_()
     outs = proj.orth_project(depth_map=d, value_map=v, valid_map=m, cam_pose=torch.tensor(POSES[b:b + 1]),
                              cam_pitch=p, cam_height=h, get_height_map=get_height)
-    loss = (torch.tensor(weights[b:b + 1]) * outs[0]).sum()
+    loss = (torch.tensor(weights[b:b + 1]) * outs[0]).sum() if loss_top else 0
     if get_height and vc:
       loss = loss + (torch.tensor(hweights[b:b + 1]) * outs[2]).sum()
     loss.backward()
@@ -193,12 +228,14 @@ def run_case(dmap, rng, case):
     grads["mask"].append(outs[1].numpy())
     grads["grad_depth"].append(d.grad.numpy())
     if v is not None:
-      grads["grad_value"].append(v.grad.numpy())
+      grads["grad_value"].append(np.zeros_like(value[b:b + 1]) if v.grad is None else v.grad.numpy())
     grads["grad_pitch"].append(p.grad.numpy())
     grads["grad_cam_height"].append(h.grad.numpy())
   for k, lst in grads.items():
     if lst:
       out[f"{name}/{k}"] = np.concatenate(lst)
+  if shared_h:                                     # one cam_height for both frames: the frames' sum
+    out[f"{name}/grad_cam_height"] = out[f"{name}/grad_cam_height"].sum(dtype=np.float32)
   cfg = dict(reduction=red, fill=np.nan if fill is None else fill, fill_is_none=fill is None,
              dmin=np.nan if dmin is None else dmin, dmax=np.nan if dmax is None else dmax,
              hmax=np.nan if hmax is None else hmax, clip=0 if clip is None else clip,
@@ -224,12 +261,13 @@ def main():
   torch.set_num_threads(1)
   torch.manual_seed(0)
   dmap = _import_reference()
-  rng = np.random.default_rng(1414)
-  arrays = {"cases": np.array([c[0] for c in CASES]),
-            **{f"cfg_{k}": np.asarray(v) for k, v in BASE.items()}}
-  for case in CASES:
-    arrays.update(run_case(dmap, rng, case))
-  save_reproducible(os.path.join(HERE, NAME + ".npz"), arrays)
+  for name, cases, seed in ((NAME, CASES, 1414), (NAME_G15, CASES_G15, 1515)):
+    rng = np.random.default_rng(seed)
+    arrays = {"cases": np.array([c[0] for c in cases]),
+              **{f"cfg_{k}": np.asarray(v) for k, v in BASE.items()}}
+    for case in cases:
+      arrays.update(run_case(dmap, rng, case))
+    save_reproducible(os.path.join(HERE, name + ".npz"), arrays)
 
 
 if __name__ == "__main__":
