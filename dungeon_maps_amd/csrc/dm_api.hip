@@ -40,6 +40,29 @@ int check_params(const dm_params* p) {
   return DM_OK;
 }
 
+// The optional input pointers against what `p` declares (a fused map and its mask go together).
+int check_inputs(const dm_params* p, const void* value_dev, const void* valid_dev, const void* fused_dev,
+                 const void* fused_mask_dev) {
+  if ((p->vc > 0) != (value_dev != nullptr))
+    return fail(DM_ERR_INVALID_ARGUMENT, "value pointer and vc=%d disagree", p->vc);
+  if ((p->valid_c > 0) != (valid_dev != nullptr))
+    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
+  if ((fused_dev != nullptr) != (fused_mask_dev != nullptr))
+    return fail(DM_ERR_INVALID_ARGUMENT, "fused map and fused mask must be given together");
+  return DM_OK;
+}
+
+int check_workspace(const void* workspace_dev, size_t workspace_bytes, size_t need) {
+  if (need > workspace_bytes || !workspace_dev)
+    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes, need);
+  return DM_OK;
+}
+
+int launch_status(hipError_t e) {
+  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
+  return DM_OK;
+}
+
 // Map widths that are not a multiple of 4 (odd ego-centric maps: 241 x 241 ...): the LDS-windowed
 // path needs 16-byte rows.  Instead of the ~9x slower generic path, the call then projects into
 // maps padded to the next multiple of 4 (workspace) and copies the real columns out: columns
@@ -125,25 +148,29 @@ static int orth_project_impl(const dm_params* p, const dm_frame* frames, const f
   if (p->B == 0) return DM_OK;
   if (!frames || !depth_dev || !out_dev || !mask_dev)
     return fail(DM_ERR_INVALID_ARGUMENT, "frames/depth/out/mask must not be NULL");
-  if ((p->vc > 0) != (value_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "value pointer and vc=%d disagree", p->vc);
-  if ((p->valid_c > 0) != (valid_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
-  if ((fused_dev != nullptr) != (fused_mask_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "fused map and fused mask must be given together");
+  if ((rc = check_inputs(p, value_dev, valid_dev, fused_dev, fused_mask_dev)) != DM_OK) return rc;
   if (fused_dev && p->reduction != DM_REDUCE_MAX && p->reduction != DM_REDUCE_MIN)
     return fail(DM_ERR_UNSUPPORTED, "the batch-fused map supports max/min only (got %d)",
                 p->reduction);
-  const size_t need = dm_orth_project_workspace_bytes(p);
-  if (need > workspace_bytes || (need && !workspace_dev))
-    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes,
-                need);
+  // (B >= 1 here, so the workspace is never empty: a NULL one is always too small)
+  if ((rc = check_workspace(workspace_dev, workspace_bytes, dm_orth_project_workspace_bytes(p))) != DM_OK)
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipErrorNotSupported;
   const hipEvent_t mid = g_mid_event, pre = g_pre_event;
   g_mid_event = nullptr;
   g_pre_event = nullptr;
   bool flowed = false;        // the projection kernel wrote the flow grid
+  // after the projection proper: record `mid`, then the batch-fused map and its mask if one was asked for
+  auto finish = [&](hipError_t r) {
+    if (r == hipSuccess && mid) r = hipEventRecord(mid, s);
+    if (r == hipSuccess && fused_dev) {
+      const size_t n = (size_t)(p->vc ? p->vc : p->dc) * p->mh * p->mw;
+      r = dm::run_fuse_batch(out_dev, p->B, n, fused_dev, p->reduction == DM_REDUCE_MAX, 0, s);
+      if (r == hipSuccess) r = dm::run_mask_from_map(fused_dev, p->fill, fused_mask_dev, n, s);
+    }
+    return r;
+  };
   if (dm::window_path_supported(*p) && !g_force_generic) {
     // the reference's default is no depth truncation at all (maps.py:1267-1268): the fast paths
     // then run with bounds beyond which no ray can still be inside the map (same cells)
@@ -183,30 +210,17 @@ static int orth_project_impl(const dm_params* p, const dm_frame* frames, const f
         hipLaunchKernelGGL(k_unpad, dim3((unsigned)blocks), dim3(256), 0, s, height_pad,
                            (const uint8_t*)nullptr, height_dev, (uint8_t*)nullptr, p->mw, q.mw, hrows);
       }
-      e = hipGetLastError();
-      if (e == hipSuccess && mid) e = hipEventRecord(mid, s);
-      if (e == hipSuccess && fused_dev) {
-        const size_t n = oc * p->mh * p->mw;
-        e = dm::run_fuse_batch(out_dev, p->B, n, fused_dev, p->reduction == DM_REDUCE_MAX, 0, s);
-        if (e == hipSuccess) e = dm::run_mask_from_map(fused_dev, p->fill, fused_mask_dev, n, s);
-      }
+      e = finish(hipGetLastError());
     }
   }
   if (e == hipErrorNotSupported) { // nothing enqueued: a window exceeds LDS, odd alignment, ...
     if (pre) (void)hipEventRecord(pre, s);
-    e = dm::run_generic(*p, frames, depth_dev, value_dev, valid_dev, out_dev, mask_dev,
-                        p->vc ? height_dev : nullptr, workspace_dev, s);
-    if (e == hipSuccess && mid) e = hipEventRecord(mid, s);
-    if (e == hipSuccess && fused_dev) {
-      const size_t n = (size_t)(p->vc ? p->vc : p->dc) * p->mh * p->mw;
-      e = dm::run_fuse_batch(out_dev, p->B, n, fused_dev, p->reduction == DM_REDUCE_MAX, 0, s);
-      if (e == hipSuccess) e = dm::run_mask_from_map(fused_dev, p->fill, fused_mask_dev, n, s);
-    }
+    e = finish(dm::run_generic(*p, frames, depth_dev, value_dev, valid_dev, out_dev, mask_dev,
+                               p->vc ? height_dev : nullptr, workspace_dev, s));
   }
   if (e == hipSuccess && grid_dev && !flowed)       // (no fused kernel for this call: the stand-alone one)
     e = dm::run_camera_affine_grid(*p, flow_frames, depth_dev, grid_dev, workspace_dev, s);
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(e);
 }
 
 extern "C" {
@@ -290,15 +304,9 @@ int dm_orth_project_prepared_f32(const dm_params* p, const dm_frames_plan* plan,
   if (rc != DM_OK) return rc;
   if (!plan || !prepared_dev || !depth_dev || !out_dev || !mask_dev || p->B < 1)
     return fail(DM_ERR_INVALID_ARGUMENT, "plan/prepared/depth/out/mask must not be NULL, B >= 1");
-  if ((p->vc > 0) != (value_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "value pointer and vc=%d disagree", p->vc);
-  if ((p->valid_c > 0) != (valid_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
-  if ((fused_dev != nullptr) != (fused_mask_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "fused map and fused mask must be given together");
-  const size_t need = dm_orth_project_workspace_bytes(p);
-  if (need > workspace_bytes || !workspace_dev)
-    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes, need);
+  if ((rc = check_inputs(p, value_dev, valid_dev, fused_dev, fused_mask_dev)) != DM_OK) return rc;
+  if ((rc = check_workspace(workspace_dev, workspace_bytes, dm_orth_project_workspace_bytes(p))) != DM_OK)
+    return rc;
   const hipEvent_t mid = g_mid_event, pre = g_pre_event;
   g_mid_event = nullptr;
   g_pre_event = nullptr;
@@ -308,8 +316,7 @@ int dm_orth_project_prepared_f32(const dm_params* p, const dm_frames_plan* plan,
                                               pre, mid, static_cast<hipStream_t>(stream));
   if (e == hipErrorNotSupported)
     return fail(DM_ERR_UNSUPPORTED, "plan does not match the parameters, or misaligned pointers");
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(e);
 }
 
 int dm_orth_project_fused_f32(const dm_params* p, const dm_frame* frames,
@@ -324,14 +331,9 @@ int dm_orth_project_fused_f32(const dm_params* p, const dm_frame* frames,
                 p->reduction);
   if (!out_dev || !mask_dev || (p->B > 0 && (!frames || !depth_dev)))
     return fail(DM_ERR_INVALID_ARGUMENT, "frames/depth/out/mask must not be NULL");
-  const size_t need = dm_orth_project_workspace_bytes(p);
-  if (need > workspace_bytes || !workspace_dev)
-    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes,
-                need);
-  if ((p->vc > 0) != (value_dev != nullptr) && p->B > 0)
-    return fail(DM_ERR_INVALID_ARGUMENT, "value pointer and vc=%d disagree", p->vc);
-  if ((p->valid_c > 0) != (valid_dev != nullptr) && p->B > 0)
-    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
+  if ((rc = check_workspace(workspace_dev, workspace_bytes, dm_orth_project_workspace_bytes(p))) != DM_OK)
+    return rc;
+  if (p->B > 0 && (rc = check_inputs(p, value_dev, valid_dev, nullptr, nullptr)) != DM_OK) return rc;
   if (p->B == 0 && !accumulate)
     return fail(DM_ERR_INVALID_ARGUMENT, "cannot fuse an empty batch without accumulate");
   hipError_t e = hipErrorNotSupported;
@@ -345,8 +347,7 @@ int dm_orth_project_fused_f32(const dm_params* p, const dm_frame* frames,
   if (e == hipErrorNotSupported)
     e = dm::run_generic_fused(*p, frames, depth_dev, value_dev, valid_dev, out_dev, mask_dev,
                               accumulate, workspace_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(e);
 }
 
 int dm_camera_affine_grid_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
@@ -359,13 +360,10 @@ int dm_camera_affine_grid_f32(const dm_params* p, const dm_frame* frames, const 
   if (p->B == 0) return DM_OK;
   if (!frames || !depth_dev || !grid_dev)
     return fail(DM_ERR_INVALID_ARGUMENT, "frames/depth/grid must not be NULL");
-  if (!workspace_dev || workspace_bytes < (size_t)p->B * sizeof(dm_frame))
-    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes,
-                (size_t)p->B * sizeof(dm_frame));
-  hipError_t e = dm::run_camera_affine_grid(*p, frames, depth_dev, grid_dev, workspace_dev,
-                                            static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  const int rc = check_workspace(workspace_dev, workspace_bytes, (size_t)p->B * sizeof(dm_frame));
+  if (rc != DM_OK) return rc;
+  return launch_status(dm::run_camera_affine_grid(*p, frames, depth_dev, grid_dev, workspace_dev,
+                                                  static_cast<hipStream_t>(stream)));
 }
 
 // Arguments both backward entry points share; every refusal happens before any HIP call.
@@ -377,10 +375,7 @@ static int check_backward(const dm_params* p, const dm_frame* frames, const floa
     return fail(DM_ERR_UNSUPPORTED, "orth_project has no backward for reduction 'prod'");
   if (p->B == 0) return DM_OK;
   if (!frames || !depth_dev) return fail(DM_ERR_INVALID_ARGUMENT, "frames/depth must not be NULL");
-  if (!workspace_dev || workspace_bytes < (size_t)p->B * sizeof(dm_frame))
-    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes,
-                (size_t)p->B * sizeof(dm_frame));
-  return DM_OK;
+  return check_workspace(workspace_dev, workspace_bytes, (size_t)p->B * sizeof(dm_frame));
 }
 
 int dm_orth_project_winners_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
@@ -388,11 +383,8 @@ int dm_orth_project_winners_f32(const dm_params* p, const dm_frame* frames, cons
                                 const float* height_dev, int32_t* winner_dev, int32_t* height_winner_dev,
                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
   int rc = check_backward(p, frames, depth_dev, workspace_dev, workspace_bytes);
+  if (rc == DM_OK) rc = check_inputs(p, value_dev, valid_dev, nullptr, nullptr);
   if (rc != DM_OK) return rc;
-  if ((p->vc > 0) != (value_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "value pointer and vc=%d disagree", p->vc);
-  if ((p->valid_c > 0) != (valid_dev != nullptr))
-    return fail(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
   if (winner_dev && p->reduction == DM_REDUCE_SUM)
     return fail(DM_ERR_INVALID_ARGUMENT, "reduction 'sum' has no winners or counts");
   if (winner_dev && p->reduction != DM_REDUCE_MEAN && !out_dev)
@@ -400,11 +392,9 @@ int dm_orth_project_winners_f32(const dm_params* p, const dm_frame* frames, cons
   if (height_winner_dev && (!p->vc || !height_dev))
     return fail(DM_ERR_INVALID_ARGUMENT, "height winners need a value map (vc > 0) and its height map");
   if (p->B == 0 || (!winner_dev && !height_winner_dev)) return DM_OK;
-  hipError_t e = dm::run_winners(*p, frames, depth_dev, value_dev, valid_dev, out_dev, height_dev,
-                                 winner_dev, height_winner_dev, workspace_dev,
-                                 static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_winners(*p, frames, depth_dev, value_dev, valid_dev, out_dev, height_dev,
+                                       winner_dev, height_winner_dev, workspace_dev,
+                                       static_cast<hipStream_t>(stream)));
 }
 
 int dm_orth_project_backward_f32(const dm_params* p, const dm_frame* frames, const float* depth_dev,
@@ -424,11 +414,9 @@ int dm_orth_project_backward_f32(const dm_params* p, const dm_frame* frames, con
   if (grad_height_dev && (!p->vc || !height_winner_dev))
     return fail(DM_ERR_INVALID_ARGUMENT, "grad_height needs a value map (vc > 0) and the height winners");
   if (p->B == 0 || (!grad_value_dev && !grad_depth_dev && !moments_dev)) return DM_OK;
-  hipError_t e = dm::run_backward(*p, frames, depth_dev, valid_dev, winner_dev, height_winner_dev,
-                                  grad_out_dev, grad_height_dev, grad_value_dev, grad_depth_dev,
-                                  moments_dev, workspace_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_backward(*p, frames, depth_dev, valid_dev, winner_dev, height_winner_dev,
+                                        grad_out_dev, grad_height_dev, grad_value_dev, grad_depth_dev,
+                                        moments_dev, workspace_dev, static_cast<hipStream_t>(stream)));
 }
 
 static int check_fuse_src(const dm_fuse_src* s) {
@@ -449,11 +437,7 @@ int dm_fuse_bbox_f32(const dm_fuse_src* src, int32_t* stats_dev, int init, void*
   if (!stats_dev) return fail(DM_ERR_INVALID_ARGUMENT, "stats is NULL");
   if (src->b == 0 || src->c == 0)
     return fail(DM_ERR_INVALID_ARGUMENT, "empty source map");
-  const dm_fuse_src& s = *src;
-  hipError_t e = hipSuccess;
-  e = dm::run_fuse_bbox(s, stats_dev, init, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_fuse_bbox(*src, stats_dev, init, static_cast<hipStream_t>(stream)));
 }
 
 int dm_fuse_scatter_f32(const dm_fuse_src* src, float width_offset, float height_offset, int flip_h,
@@ -468,11 +452,9 @@ int dm_fuse_scatter_f32(const dm_fuse_src* src, float width_offset, float height
                 (long long)map_width);
   if (src->b == 0 || src->c == 0) return DM_OK;
   if (!canvas_dev) return fail(DM_ERR_INVALID_ARGUMENT, "canvas is NULL");
-  hipError_t e = dm::run_fuse_scatter(*src, width_offset, height_offset, flip_h, (int)map_height,
-                                      (int)map_width, reduction == DM_REDUCE_MAX, canvas_dev,
-                                      height_canvas_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_fuse_scatter(*src, width_offset, height_offset, flip_h, (int)map_height,
+                                            (int)map_width, reduction == DM_REDUCE_MAX, canvas_dev,
+                                            height_canvas_dev, static_cast<hipStream_t>(stream)));
 }
 
 static int check_fuse_sources(const dm_fuse_src* srcs, int32_t n) {
@@ -494,9 +476,7 @@ int dm_fuse_bbox_multi_f32(const dm_fuse_src* srcs, int32_t n, int32_t* stats_de
   const int rc = check_fuse_sources(srcs, n);
   if (rc != DM_OK) return rc;
   if (!stats_dev) return fail(DM_ERR_INVALID_ARGUMENT, "stats is NULL");
-  const hipError_t e = dm::run_fuse_bbox_multi(srcs, n, stats_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_fuse_bbox_multi(srcs, n, stats_dev, static_cast<hipStream_t>(stream)));
 }
 
 int dm_fuse_bbox_read_i32(const int32_t* stats_dev, int32_t* stats_host, void* stream) {
@@ -530,11 +510,9 @@ int dm_fuse_scatter_multi_f32(const dm_fuse_src* srcs, int32_t n, float width_of
     return fail(DM_ERR_INVALID_ARGUMENT, "bad target size %lldx%lld", (long long)map_height,
                 (long long)map_width);
   if (!canvas_dev) return fail(DM_ERR_INVALID_ARGUMENT, "canvas is NULL");
-  const hipError_t e = dm::run_fuse_scatter_multi(srcs, n, width_offset, height_offset, flip_h, (int)map_height,
+  return launch_status(dm::run_fuse_scatter_multi(srcs, n, width_offset, height_offset, flip_h, (int)map_height,
                                                   (int)map_width, reduction == DM_REDUCE_MAX, canvas_dev,
-                                                  height_canvas_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+                                                  height_canvas_dev, static_cast<hipStream_t>(stream)));
 }
 
 int dm_crop_nearest_f32(const float* image_dev, const uint8_t* mask_dev, const float* center_dev,
@@ -549,11 +527,9 @@ int dm_crop_nearest_f32(const float* image_dev, const uint8_t* mask_dev, const f
   if (B == 0 || C == 0 || crop_h == 0 || crop_w == 0) return DM_OK;
   if (!image_dev || !center_dev || !out_dev || (mask_dev != nullptr) != (out_mask_dev != nullptr))
     return fail(DM_ERR_INVALID_ARGUMENT, "image/center/out must not be NULL; mask and out_mask go together");
-  hipError_t e = dm::run_crop_nearest(image_dev, mask_dev, center_dev, (int)B, (int)C, (int)h, (int)w,
-                                      (int)crop_h, (int)crop_w, fill, has_fill, out_dev,
-                                      out_mask_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_crop_nearest(image_dev, mask_dev, center_dev, (int)B, (int)C, (int)h, (int)w,
+                                            (int)crop_h, (int)crop_w, fill, has_fill, out_dev,
+                                            out_mask_dev, static_cast<hipStream_t>(stream)));
 }
 
 int dm_crop_sample_f32(const float* image_dev, const uint8_t* mask_dev, const float* center_dev,
@@ -573,11 +549,9 @@ int dm_crop_sample_f32(const float* image_dev, const uint8_t* mask_dev, const fl
   if (B == 0 || C == 0 || crop_h == 0 || crop_w == 0) return DM_OK;
   if (!image_dev || !center_dev || !out_dev || (mask_dev != nullptr) != (out_mask_dev != nullptr))
     return fail(DM_ERR_INVALID_ARGUMENT, "image/center/out must not be NULL; mask and out_mask go together");
-  hipError_t e = dm::run_crop_interp(image_dev, mask_dev, center_dev, (int)B, (int)C, (int)h, (int)w, (int)crop_h,
-                                     (int)crop_w, fill, has_fill, mode, out_dev, out_mask_dev,
-                                     static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_crop_interp(image_dev, mask_dev, center_dev, (int)B, (int)C, (int)h, (int)w, (int)crop_h,
+                                           (int)crop_w, fill, has_fill, mode, out_dev, out_mask_dev,
+                                           static_cast<hipStream_t>(stream)));
 }
 
 int dm_affine_points_f32(const float* pts_dev, const float* R_dev, const float* t_dev, int64_t B,
@@ -586,10 +560,8 @@ int dm_affine_points_f32(const float* pts_dev, const float* R_dev, const float* 
   if (B == 0 || n == 0) return DM_OK;
   if (!pts_dev || !R_dev || !t_dev || !out_dev)
     return fail(DM_ERR_INVALID_ARGUMENT, "pts/R/t/out must not be NULL");
-  hipError_t e = dm::run_affine_points(pts_dev, R_dev, t_dev, (int)B, n, translate_first, out_dev,
-                                       static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_affine_points(pts_dev, R_dev, t_dev, (int)B, n, translate_first, out_dev,
+                                             static_cast<hipStream_t>(stream)));
 }
 
 int dm_map_quantize_f32(const float* x_dev, const float* z_dev, const float* woff_dev,
@@ -599,12 +571,10 @@ int dm_map_quantize_f32(const float* x_dev, const float* z_dev, const float* wof
   if (B == 0 || n == 0) return DM_OK;
   if (!x_dev || !z_dev || !woff_dev || !hoff_dev || !xb_dev || !zb_dev)
     return fail(DM_ERR_INVALID_ARGUMENT, "x/z/offsets/outputs must not be NULL");
-  hipError_t e = dm::run_map_quantize(x_dev, z_dev, woff_dev, hoff_dev, (int)B, n, res, map_height,
-                                      flip_h != 0, reinterpret_cast<long long*>(xb_dev),
-                                      reinterpret_cast<long long*>(zb_dev),
-                                      static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_map_quantize(x_dev, z_dev, woff_dev, hoff_dev, (int)B, n, res, map_height,
+                                            flip_h != 0, reinterpret_cast<long long*>(xb_dev),
+                                            reinterpret_cast<long long*>(zb_dev),
+                                            static_cast<hipStream_t>(stream)));
 }
 
 size_t dm_scatter_workspace_bytes(int64_t R, int32_t C, size_t M, int32_t has_fill,
@@ -629,11 +599,9 @@ int dm_scatter_f32(const float* values_dev, const int64_t* index_dev, float* can
   if (need > workspace_bytes || (need && !workspace_dev))
     return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes,
                 need);
-  hipError_t e = dm::run_scatter(values_dev, reinterpret_cast<const long long*>(index_dev),
-                                 canvas_dev, mask_dev, (int)R, C, Ci, N, M, fill, has_fill != 0,
-                                 reduction, workspace_dev, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_scatter(values_dev, reinterpret_cast<const long long*>(index_dev),
+                                       canvas_dev, mask_dev, (int)R, C, Ci, N, M, fill, has_fill != 0,
+                                       reduction, workspace_dev, static_cast<hipStream_t>(stream)));
 }
 
 void dm_debug_record_before_projection(void* event) {
@@ -658,20 +626,16 @@ int dm_fuse_batch_f32(const float* maps_dev, int64_t B, size_t n, float* out_dev
   if (n == 0 || (B == 0 && accumulate)) return DM_OK;
   if (B == 0) return fail(DM_ERR_INVALID_ARGUMENT, "cannot fuse an empty batch without accumulate");
   if (!maps_dev || !out_dev) return fail(DM_ERR_INVALID_ARGUMENT, "maps/out must not be NULL");
-  hipError_t e = dm::run_fuse_batch(maps_dev, (int)B, n, out_dev, reduction == DM_REDUCE_MAX,
-                                    accumulate, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_fuse_batch(maps_dev, (int)B, n, out_dev, reduction == DM_REDUCE_MAX,
+                                          accumulate, static_cast<hipStream_t>(stream)));
 }
 
 int dm_mask_from_map_f32(const float* map_dev, float fill, uint8_t* mask_dev, size_t n,
                          void* stream) {
   if (n == 0) return DM_OK;
   if (!map_dev || !mask_dev) return fail(DM_ERR_INVALID_ARGUMENT, "map/mask must not be NULL");
-  hipError_t e = dm::run_mask_from_map(map_dev, fill, mask_dev, n,
-                                       static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(dm::run_mask_from_map(map_dev, fill, mask_dev, n,
+                                             static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -154,11 +154,9 @@ class _Call:
       if self.valid.shape[0] != B:
         self.valid = self.valid.expand(B, -1, -1, -1).contiguous()
       valid_c = self.valid.shape[1]
-    key = (B, dc, vc, H, W, int(map_height), int(map_width),
-           int(clip_border) if clip_border is not None else 0, bool(flip_h), bool(to_global),
-           _reduction_code(reduction), trunc_depth_min, trunc_depth_max, trunc_height_max,
-           valid_c, float(center_x), float(center_y), float(focal_x), float(focal_y),
-           float(map_res), fill_value)
+    key = _params_key(B, dc, vc, H, W, map_height, map_width, clip_border, flip_h, to_global, reduction,
+                      trunc_depth_min, trunc_depth_max, trunc_height_max, valid_c, center_x, center_y,
+                      focal_x, focal_y, map_res, fill_value)
     cached = _PARAMS_CACHE.get(key)
     if cached is None:
       cached = _make_params(key)
@@ -197,8 +195,17 @@ _WS_LOCAL = threading.local()     # .kept: (GPU index, stream) -> uint8 workspac
 _PARAMS_CACHE = {}   # call signature -> (dm_params, workspace bytes); both immutable afterwards
 
 
+def _params_key(B, dc, vc, H, W, map_height, map_width, clip_border, flip_h, to_global, reduction,
+                trunc_depth_min, trunc_depth_max, trunc_height_max, valid_c, center_x, center_y,
+                focal_x, focal_y, map_res, fill_value):
+  """One dm_params as _make_params takes it and _PARAMS_CACHE keys it (the shapes: ints)."""
+  return (B, dc, vc, H, W, int(map_height), int(map_width),
+          int(clip_border) if clip_border is not None else 0, bool(flip_h), bool(to_global),
+          _reduction_code(reduction), trunc_depth_min, trunc_depth_max, trunc_height_max, valid_c,
+          float(center_x), float(center_y), float(focal_x), float(focal_y), float(map_res), fill_value)
+
+
 def _make_params(key):
-  import ctypes
   (B, dc, vc, H, W, mh, mw, clip, flip_h, to_global, red, dmin, dmax, hmax, valid_c, cx, cy,
    fx, fy, res, fill) = key
   p = _native.Params()
@@ -227,6 +234,56 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
   return None if t is None else t.data_ptr()
 
 
+def _empty_maps(shape, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+  return (torch.empty(shape, dtype=torch.float32, device=dev),
+          torch.empty(shape, dtype=torch.bool, device=dev))
+
+
+def _maps_out(out, shape, dev, what) -> Tuple[torch.Tensor, torch.Tensor]:
+  """The (float32 map, bool mask) pair a call writes: the caller's ``out`` (argument ``what``),
+  checked, or a fresh pair."""
+  if out is None:
+    return _empty_maps(shape, dev)
+  top, mask = out
+  for t, dt in ((top, torch.float32), (mask, torch.bool)):
+    if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+      raise ValueError(f"`{what}` must be contiguous {dt} {shape} tensors on {dev}")
+  return top, mask
+
+
+def _height_map(p, dev, get_height_map) -> Optional[torch.Tensor]:
+  """The separate (B, dc, mh, mw) height map: asked for and the call projects a value map."""
+  if get_height_map and p.vc:
+    return torch.empty((p.B, p.dc, p.mh, p.mw), dtype=torch.float32, device=dev)
+  return None
+
+
+def _with_height(topdown, mask, height, get_height_map):
+  """orth_project's return: ``(topdown, mask)``, plus the height map when asked for -- topdown
+  itself without a value map, else the height map broadcast over the value channels."""
+  if not get_height_map:
+    return topdown, mask
+  return topdown, mask, (topdown if height is None else torch.broadcast_to(height, topdown.shape))
+
+
+def _to_target(call, *tensors):
+  """The outputs on the device the caller's tensors live on (maps.py:227-232)."""
+  if call.target != call.dev:
+    return tuple(None if t is None else t.to(call.target) for t in tensors)
+  return tensors
+
+
+def _launch(call, depth, value, topdown, mask, height, fused=None, fused_mask=None) -> None:
+  """Enqueue dm_orth_project_f32 for ``call`` on the current stream of its GPU."""
+  ws, ws_bytes = call.workspace()
+  _native.check_status()
+  with _on_device(call.dev):
+    _native.check(_native.lib().dm_orth_project_f32(
+        ctypes.byref(call.params), _ptr(call.frames), _ptr(depth), _ptr(value), _ptr(call.valid),
+        _ptr(topdown), _ptr(mask), _ptr(height), _ptr(fused), _ptr(fused_mask), _ptr(ws), ws_bytes,
+        _native.status_ptr(), _stream_ptr(call.dev)))
+
+
 def orth_project(
     depth_map, value_map, valid_map, cam_pose, width_offset, height_offset, cam_pitch,
     cam_height, map_res: float, map_width: int, map_height: int, focal_x: float,
@@ -250,18 +307,15 @@ def orth_project(
   unproject, pitch/yaw/translate, truncations, quantisation, scatter-reduce and
   the changed-mask (dm_orth_project_f32).
   """
-  if torch.is_grad_enabled() and _wants_grad(depth_map, value_map, cam_pitch, cam_height) \
-      and Reduction(reduction) is not Reduction.prod:
-    return _orth_project_grad(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-                              cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-                              center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-                              clip_border, to_global, flip_h, fill_value, reduction, get_height_map,
-                              device)
-  return _orth_project(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-                       cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-                       center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-                       clip_border, to_global, flip_h, fill_value, reduction, get_height_map,
-                       device, False, None, None)
+  grad = torch.is_grad_enabled() and _wants_grad(depth_map, value_map, cam_pitch, cam_height) \
+      and Reduction(reduction) is not Reduction.prod
+  call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset, cam_pitch,
+               cam_height, map_res, map_width, map_height, focal_x, focal_y, center_x, center_y,
+               trunc_depth_min, trunc_depth_max, trunc_height_max, clip_border, to_global, flip_h,
+               fill_value, reduction, device)
+  if grad:
+    return _orth_project_grad(call, cam_pitch, cam_height, get_height_map)
+  return _orth_project(call, get_height_map, False, None, None)
 
 
 # ---------------------------------------------------------------------------
@@ -300,19 +354,9 @@ class _OrthProjectFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, call, get_height, depth, value, pitch, cam_h):
     p = call.params
-    shape = (p.B, call.oc, p.mh, p.mw)
-    topdown = torch.empty(shape, dtype=torch.float32, device=call.dev)
-    mask = torch.empty(shape, dtype=torch.bool, device=call.dev)
-    height = None
-    if get_height and p.vc:
-      height = torch.empty((p.B, p.dc, p.mh, p.mw), dtype=torch.float32, device=call.dev)
-    ws, ws_bytes = call.workspace()
-    _native.check_status()
-    with _on_device(call.dev):
-      _native.check(_native.lib().dm_orth_project_f32(
-          ctypes.byref(p), _ptr(call.frames), _ptr(depth), _ptr(value), _ptr(call.valid),
-          _ptr(topdown), _ptr(mask), _ptr(height), None, None, _ptr(ws), ws_bytes,
-          _native.status_ptr(), _stream_ptr(call.dev)))
+    topdown, mask = _empty_maps((p.B, call.oc, p.mh, p.mw), call.dev)
+    height = _height_map(p, call.dev, get_height)
+    _launch(call, depth, value, topdown, mask, height)
     ctx.call = call
     ctx.pitch = None if pitch is None else pitch.detach()
     ctx.mark_non_differentiable(mask)
@@ -395,85 +439,30 @@ def _camera_grads(moments, pitch, B, dev, need_pitch, need_h):
   return g_p, g_h
 
 
-def _orth_project_grad(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-                       cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-                       center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-                       clip_border, to_global, flip_h, fill_value, reduction, get_height_map, device):
+def _orth_project_grad(call, cam_pitch, cam_height, get_height_map):
   """orth_project through _OrthProjectFn.  The dtype / device / layout conversions happen in
   _Call with torch ops (autograd sees them); so does the copy back to a CPU target."""
-  call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-               cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-               center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-               clip_border, to_global, flip_h, fill_value, reduction, device)
   B = call.params.B
   pitch = _frame_column(cam_pitch, B, call.dev)
   cam_h = _frame_column(cam_height, B, call.dev)
   outs = _OrthProjectFn.apply(call, bool(get_height_map), call.depth, call.value, pitch, cam_h)
-  topdown, mask = outs[0], outs[1]
-  height = outs[2] if len(outs) > 2 else None
-  if call.target != call.dev:
-    topdown, mask = topdown.to(call.target), mask.to(call.target)
-    height = None if height is None else height.to(call.target)
-  if not get_height_map:
-    return topdown, mask
-  if height is None:
-    return topdown, mask, topdown
-  return topdown, mask, torch.broadcast_to(height, topdown.shape)
+  topdown, mask, height = _to_target(call, outs[0], outs[1], outs[2] if len(outs) > 2 else None)
+  return _with_height(topdown, mask, height, get_height_map)
 
 
-def _orth_project(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-                  cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-                  center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-                  clip_border, to_global, flip_h, fill_value, reduction, get_height_map, device,
-                  _fuse, _fused_out, _out):
+def _orth_project(call, get_height_map, _fuse, _fused_out, _out):
   """orth_project / orth_project_and_fuse behind one native call."""
-  import ctypes
-  call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-               cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-               center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-               clip_border, to_global, flip_h, fill_value, reduction, device)
   p = call.params
-  shape = (p.B, call.oc, p.mh, p.mw)
-  if _out is not None:
-    topdown, mask = _out
-    for t, dt in ((topdown, torch.float32), (mask, torch.bool)):
-      if tuple(t.shape) != shape or t.dtype != dt or t.device != call.dev or not t.is_contiguous():
-        raise ValueError(f"`out` must be contiguous {dt} {shape} tensors on {call.dev}")
-  else:
-    topdown = torch.empty(shape, dtype=torch.float32, device=call.dev)
-    mask = torch.empty(shape, dtype=torch.bool, device=call.dev)
-  height = None
-  if get_height_map and p.vc:
-    height = torch.empty((p.B, p.dc, p.mh, p.mw), dtype=torch.float32, device=call.dev)
+  topdown, mask = _maps_out(_out, (p.B, call.oc, p.mh, p.mw), call.dev, "out")
+  height = _height_map(p, call.dev, get_height_map)
   fused = fmask = None
-  if _fuse and _fused_out is not None:
-    fused, fmask = _fused_out
-    for t, dt in ((fused, torch.float32), (fmask, torch.bool)):
-      if tuple(t.shape) != shape[1:] or t.dtype != dt or t.device != call.dev \
-          or not t.is_contiguous():
-        raise ValueError(f"`fused_out` must be contiguous {dt} {shape[1:]} tensors on {call.dev}")
-  elif _fuse:
-    fused = torch.empty(shape[1:], dtype=torch.float32, device=call.dev)
-    fmask = torch.empty(shape[1:], dtype=torch.bool, device=call.dev)
-  ws, ws_bytes = call.workspace()
-  _native.check_status()
-  with _on_device(call.dev):
-    _native.check(_native.lib().dm_orth_project_f32(
-        ctypes.byref(p), _ptr(call.frames), _ptr(call.depth), _ptr(call.value),
-        _ptr(call.valid), _ptr(topdown), _ptr(mask), _ptr(height), _ptr(fused), _ptr(fmask),
-        _ptr(ws), ws_bytes, _native.status_ptr(), _stream_ptr(call.dev)))
-  if call.target != call.dev:
-    topdown, mask = topdown.to(call.target), mask.to(call.target)
-    height = None if height is None else height.to(call.target)
-    if _fuse:
-      fused, fmask = fused.to(call.target), fmask.to(call.target)
   if _fuse:
-    return topdown, mask, fused, fmask
-  if not get_height_map:
-    return topdown, mask
-  if height is None:
-    return topdown, mask, topdown
-  return topdown, mask, torch.broadcast_to(height, topdown.shape)
+    fused, fmask = _maps_out(_fused_out, (call.oc, p.mh, p.mw), call.dev, "fused_out")
+  _launch(call, call.depth, call.value, topdown, mask, height, fused, fmask)
+  if _fuse:
+    return _to_target(call, topdown, mask, fused, fmask)
+  topdown, mask, height = _to_target(call, topdown, mask, height)
+  return _with_height(topdown, mask, height, get_height_map)
 
 
 def orth_project_and_fuse(depth_map, value_map, valid_map, cam_pose, width_offset,
@@ -494,11 +483,11 @@ def orth_project_and_fuse(depth_map, value_map, valid_map, cam_pose, width_offse
   steps (fewer, larger collectives).  ``out`` = (float32 (b,C,mh,mw), bool (b,C,mh,mw)) does
   the same for the per-frame maps and masks (a caller that keeps a ring of output sets pays no
   allocation per call)."""
-  return _orth_project(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
-                       cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
-                       center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
-                       clip_border, to_global, flip_h, fill_value, reduction, False, device,
-                       True, fused_out, out)
+  call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset, cam_pitch,
+               cam_height, map_res, map_width, map_height, focal_x, focal_y, center_x, center_y,
+               trunc_depth_min, trunc_depth_max, trunc_height_max, clip_border, to_global, flip_h,
+               fill_value, reduction, device)
+  return _orth_project(call, False, True, fused_out, out)
 
 
 def orth_project_and_flow(depth_map, trans_pose, valid_map, cam_pose, width_offset, height_offset,
@@ -523,15 +512,7 @@ def orth_project_and_flow(depth_map, trans_pose, valid_map, cam_pose, width_offs
                clip_border, to_global, flip_h, fill_value, reduction, device)
   p = call.params
   B, dc, H, W = call.depth.shape
-  shape = (p.B, call.oc, p.mh, p.mw)
-  if out is not None:
-    topdown, mask = out
-    for t, dt in ((topdown, torch.float32), (mask, torch.bool)):
-      if tuple(t.shape) != shape or t.dtype != dt or t.device != call.dev or not t.is_contiguous():
-        raise ValueError(f"`out` must be contiguous {dt} {shape} tensors on {call.dev}")
-  else:
-    topdown = torch.empty(shape, dtype=torch.float32, device=call.dev)
-    mask = torch.empty(shape, dtype=torch.bool, device=call.dev)
+  topdown, mask = _maps_out(out, (p.B, call.oc, p.mh, p.mw), call.dev, "out")
   flow_table = frames.build_frame_table(B, trans_pose, cam_pitch, cam_height, 0., 0., inverse_pitch=True)
   grid = torch.empty((B, dc, H, W, 2), dtype=torch.float32, device=call.dev)
   ws_bytes = max(call.ws_bytes, B * _native.FRAME_FLOATS * 4)
@@ -542,9 +523,7 @@ def orth_project_and_flow(depth_map, trans_pose, valid_map, cam_pose, width_offs
         ctypes.byref(p), _ptr(call.frames), _ptr(flow_table), _ptr(call.depth), _ptr(call.valid),
         _ptr(topdown), _ptr(mask), None, None, _ptr(grid), _ptr(ws), ws_bytes, _native.status_ptr(),
         _stream_ptr(call.dev)))
-  if call.target != call.dev:
-    topdown, mask, grid = topdown.to(call.target), mask.to(call.target), grid.to(call.target)
-  return topdown, mask, grid
+  return _to_target(call, topdown, mask, grid)
 
 
 def orth_project_fused(
@@ -562,7 +541,6 @@ def orth_project_fused(
   resolution/offsets/size (element-wise max).  ``out`` (C, mh, mw),
   if given, is the running world map: its content takes part in the reduction.
   """
-  import ctypes
   call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
                cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
                center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
@@ -584,9 +562,7 @@ def orth_project_fused(
         ctypes.byref(p), _ptr(call.frames), _ptr(call.depth), _ptr(call.value),
         _ptr(call.valid), _ptr(out), _ptr(mask), int(accumulate), _ptr(ws), ws_bytes,
         _native.status_ptr(), _stream_ptr(call.dev)))
-  if call.target != call.dev:       # outputs live on the depth map's device (maps.py:227-232)
-    out, mask = out.to(call.target), mask.to(call.target)
-  return out, mask
+  return _to_target(call, out, mask)
 
 
 class PreparedProjection:
@@ -610,18 +586,16 @@ class PreparedProjection:
                width_offset, height_offset, cam_pitch, cam_height, map_res, map_width, map_height,
                focal_x, focal_y, center_x, center_y, trunc_depth_min, trunc_depth_max,
                trunc_height_max, clip_border, to_global, flip_h, fill_value, reduction, device):
-    import ctypes
     dev = _compute_device(torch.device(device) if device is not None else torch.device("cuda"))
     self.dev = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
     self.shape_in = (int(batch), int(depth_channels), int(height), int(width))
     self.vc, self.valid_c = int(value_channels), int(valid_channels)
-    key = (int(batch), int(depth_channels), self.vc, int(height), int(width), int(map_height),
-           int(map_width), int(clip_border) if clip_border is not None else 0, bool(flip_h),
-           bool(to_global), _reduction_code(reduction), trunc_depth_min, trunc_depth_max,
-           trunc_height_max, self.valid_c, float(center_x), float(center_y), float(focal_x),
-           float(focal_y), float(map_res), fill_value)
-    self.params, self.ws_bytes = _make_params(key)
-    self.oc = self.vc if self.vc else int(depth_channels)
+    B, dc, H, W = self.shape_in
+    self.params, self.ws_bytes = _make_params(_params_key(
+        B, dc, self.vc, H, W, map_height, map_width, clip_border, flip_h, to_global, reduction,
+        trunc_depth_min, trunc_depth_max, trunc_height_max, self.valid_c, center_x, center_y, focal_x,
+        focal_y, map_res, fill_value))
+    self.oc = self.vc if self.vc else dc
     self.fill_value = fill_value
     self._camera = dict(cam_pitch=cam_pitch, cam_height=cam_height, width_offset=width_offset,
                         height_offset=height_offset)
@@ -641,7 +615,6 @@ class PreparedProjection:
     """Upload other poses (and optionally ``cam_pitch`` / ``cam_height`` / offsets) for the same
     shapes.  Raises -- before anything is written to the device -- if they need a different
     launch plan than the one in use (e.g. another pitch: make a new PreparedProjection)."""
-    import ctypes
     camera = {k: v for k, v in camera.items() if v is not None}
     unknown = set(camera) - set(self._camera)
     if unknown:
@@ -676,7 +649,6 @@ class PreparedProjection:
                        f"{(B, channels, H, W)} on {self.dev}")
 
   def _run(self, depth_map, value_map, valid_map, out, height, fused):
-    import ctypes
     p = self.params
     self._check(depth_map, self.shape_in[1], torch.float32, "depth_map")
     if (value_map is not None) != bool(self.vc):
@@ -687,11 +659,7 @@ class PreparedProjection:
       raise ValueError(f"prepared for {self.valid_c} valid-map channels")
     if valid_map is not None:
       self._check(valid_map, self.valid_c, torch.bool, "valid_map")
-    shape = (p.B, self.oc, p.mh, p.mw)
-    if out is None:
-      out = (torch.empty(shape, dtype=torch.float32, device=self.dev),
-             torch.empty(shape, dtype=torch.bool, device=self.dev))
-    top, mask = out
+    top, mask = out if out is not None else _empty_maps((p.B, self.oc, p.mh, p.mw), self.dev)
     _native.check_status()
     with _on_device(self.dev):
       _native.check(_native.lib().dm_orth_project_prepared_f32(
@@ -705,22 +673,16 @@ class PreparedProjection:
     """``orth_project`` of GPU tensors with the prepared camera state: ``(topdown, mask[,
     height_map])``.  ``out`` = (float32, bool) tensors of shape (b, C, mh, mw) to write into
     (static outputs, e.g. under graph capture)."""
-    height = None
-    if get_height_map and self.vc:
-      height = torch.empty((self.params.B, self.shape_in[1], self.params.mh, self.params.mw),
-                           dtype=torch.float32, device=self.dev)
+    height = _height_map(self.params, self.dev, get_height_map)
     top, mask = self._run(depth_map, value_map, valid_map, out, height, None)
-    if not get_height_map:
-      return top, mask
-    return top, mask, (top if height is None else torch.broadcast_to(height, top.shape))
+    return _with_height(top, mask, height, get_height_map)
 
   def orth_project_and_fuse(self, depth_map, value_map=None, valid_map=None, out=None, fused_out=None):
     """Per-frame maps plus the batch-fused map (max / min over the frames):
     ``(topdown, mask, fused, fused_mask)``."""
     p = self.params
     if fused_out is None:
-      fused_out = (torch.empty((self.oc, p.mh, p.mw), dtype=torch.float32, device=self.dev),
-                   torch.empty((self.oc, p.mh, p.mw), dtype=torch.bool, device=self.dev))
+      fused_out = _empty_maps((self.oc, p.mh, p.mw), self.dev)
     top, mask = self._run(depth_map, value_map, valid_map, out, None, fused_out)
     return top, mask, fused_out[0], fused_out[1]
 

@@ -99,3 +99,172 @@ def test_product_does_not_import_the_oracle():
     if f.endswith((".py", ".sh", ".hip", ".c")):
       text = open(os.path.join(tools, f)).read()
       assert "import oracle" not in text and "from oracle" not in text, f"tools/{f} uses the oracle"
+
+
+# Status codes of the projection entry points for bad arguments, one row per case the C layer
+# tells apart.  Every row is refused (or returns DM_OK for an empty batch) before any HIP call,
+# so the pointers are never dereferenced.
+_PTR = 4096          # a stand-in device address
+_ARGS = {
+    "dm_orth_project_f32": ("frames", "depth", "value", "valid", "out", "mask", "height", "fused",
+                            "fused_mask", "ws", "ws_bytes", "status", "stream"),
+    "dm_orth_project_flow_f32": ("frames", "flow_frames", "depth", "valid", "out", "mask", "fused",
+                                 "fused_mask", "grid", "ws", "ws_bytes", "status", "stream"),
+    "dm_orth_project_prepared_f32": ("plan", "prepared", "depth", "value", "valid", "out", "mask",
+                                     "height", "fused", "fused_mask", "ws", "ws_bytes", "status",
+                                     "stream"),
+    "dm_orth_project_fused_f32": ("frames", "depth", "value", "valid", "out", "mask", "accumulate",
+                                  "ws", "ws_bytes", "status", "stream"),
+    "dm_orth_project_winners_f32": ("frames", "depth", "value", "valid", "out", "height", "winner",
+                                    "height_winner", "ws", "ws_bytes", "stream"),
+    "dm_orth_project_backward_f32": ("frames", "depth", "valid", "winner", "height_winner",
+                                     "grad_out", "grad_height", "grad_value", "grad_depth",
+                                     "moments", "ws", "ws_bytes", "stream"),
+}
+# pointers every call of that entry point passes unless a case overrides them
+_GIVEN = {
+    "dm_orth_project_f32": ("frames", "depth", "out", "mask"),
+    "dm_orth_project_flow_f32": ("frames", "flow_frames", "depth", "out", "mask", "grid"),
+    "dm_orth_project_prepared_f32": ("plan", "prepared", "depth", "out", "mask"),
+    "dm_orth_project_fused_f32": ("frames", "depth", "out", "mask"),
+    "dm_orth_project_winners_f32": ("frames", "depth", "out", "winner"),
+    "dm_orth_project_backward_f32": ("frames", "depth", "winner", "grad_out", "grad_depth"),
+}
+MAX, MIN, SUM, MEAN, PROD = range(5)
+OK, INVALID, UNSUPPORTED, WORKSPACE = 0, -1, -2, -3
+_REFUSALS = [
+    # (entry point, dm_params fields, arguments, status)
+    ("dm_orth_project_f32", {"reduction": 9}, {}, INVALID),
+    ("dm_orth_project_f32", {"B": 0}, {"frames": None, "depth": None, "out": None, "mask": None, "ws": None}, OK),
+    ("dm_orth_project_f32", {}, {"frames": None}, INVALID),
+    ("dm_orth_project_f32", {}, {"depth": None}, INVALID),
+    ("dm_orth_project_f32", {}, {"out": None}, INVALID),
+    ("dm_orth_project_f32", {}, {"mask": None}, INVALID),
+    ("dm_orth_project_f32", {}, {"value": _PTR}, INVALID),
+    ("dm_orth_project_f32", {"vc": 2}, {}, INVALID),
+    ("dm_orth_project_f32", {}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_f32", {"valid_c": 1}, {}, INVALID),
+    ("dm_orth_project_f32", {}, {"fused": _PTR}, INVALID),
+    ("dm_orth_project_f32", {}, {"fused_mask": _PTR}, INVALID),
+    ("dm_orth_project_f32", {"reduction": SUM}, {"fused": _PTR, "fused_mask": _PTR}, UNSUPPORTED),
+    ("dm_orth_project_f32", {"reduction": MEAN}, {"fused": _PTR, "fused_mask": _PTR}, UNSUPPORTED),
+    ("dm_orth_project_f32", {"reduction": SUM}, {"fused": _PTR, "fused_mask": _PTR, "value": _PTR}, INVALID),
+    ("dm_orth_project_f32", {}, {"ws_bytes": -1}, WORKSPACE),
+    ("dm_orth_project_f32", {}, {"ws": None}, WORKSPACE),
+    ("dm_orth_project_f32", {"vc": 1}, {"value": _PTR, "ws_bytes": -1}, WORKSPACE),
+    # flow: vc != 0 is refused before anything else, then the flow pointers, then B == 0
+    ("dm_orth_project_flow_f32", {"vc": 1, "reduction": 9}, {}, INVALID),
+    ("dm_orth_project_flow_f32", {"vc": 1, "B": 0}, {}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"flow_frames": None}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"grid": None}, INVALID),
+    ("dm_orth_project_flow_f32", {"B": 0}, {"grid": None}, INVALID),
+    ("dm_orth_project_flow_f32", {"B": 0, "reduction": 9}, {"frames": None, "depth": None, "ws": None}, OK),
+    ("dm_orth_project_flow_f32", {"reduction": 9}, {}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"frames": None}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"depth": None}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"out": None}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"mask": None}, INVALID),
+    ("dm_orth_project_flow_f32", {"valid_c": 1}, {}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_flow_f32", {}, {"fused": _PTR}, INVALID),
+    ("dm_orth_project_flow_f32", {"reduction": SUM}, {"fused": _PTR, "fused_mask": _PTR}, UNSUPPORTED),
+    ("dm_orth_project_flow_f32", {}, {"ws_bytes": -1}, WORKSPACE),
+    ("dm_orth_project_flow_f32", {}, {"ws": None}, WORKSPACE),
+    # prepared: B >= 1, and a NULL workspace is refused whatever it needs
+    ("dm_orth_project_prepared_f32", {"reduction": 9}, {}, INVALID),
+    ("dm_orth_project_prepared_f32", {"B": 0}, {}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"plan": None}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"prepared": None}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"depth": None}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"out": None}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"mask": None}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"value": _PTR}, INVALID),
+    ("dm_orth_project_prepared_f32", {"vc": 1}, {}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_prepared_f32", {"valid_c": 1}, {}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"fused": _PTR}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"fused_mask": _PTR}, INVALID),
+    ("dm_orth_project_prepared_f32", {}, {"ws_bytes": -1}, WORKSPACE),
+    ("dm_orth_project_prepared_f32", {}, {"ws": None}, WORKSPACE),
+    # fused: the reduction first, then NULL pointers, the workspace, value / valid only when B > 0
+    ("dm_orth_project_fused_f32", {"reduction": SUM}, {"frames": None, "depth": None, "out": None, "mask": None}, UNSUPPORTED),
+    ("dm_orth_project_fused_f32", {"reduction": MEAN}, {}, UNSUPPORTED),
+    ("dm_orth_project_fused_f32", {"reduction": PROD}, {}, UNSUPPORTED),
+    ("dm_orth_project_fused_f32", {"reduction": 9}, {}, INVALID),
+    ("dm_orth_project_fused_f32", {}, {"out": None}, INVALID),
+    ("dm_orth_project_fused_f32", {}, {"mask": None}, INVALID),
+    ("dm_orth_project_fused_f32", {}, {"frames": None}, INVALID),
+    ("dm_orth_project_fused_f32", {}, {"depth": None}, INVALID),
+    ("dm_orth_project_fused_f32", {}, {"ws_bytes": -1}, WORKSPACE),
+    ("dm_orth_project_fused_f32", {}, {"ws": None}, WORKSPACE),
+    ("dm_orth_project_fused_f32", {}, {"ws": None, "value": _PTR}, WORKSPACE),
+    ("dm_orth_project_fused_f32", {}, {"value": _PTR}, INVALID),
+    ("dm_orth_project_fused_f32", {"vc": 1}, {}, INVALID),
+    ("dm_orth_project_fused_f32", {}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_fused_f32", {"valid_c": 1}, {}, INVALID),
+    ("dm_orth_project_fused_f32", {"B": 0}, {"frames": None, "depth": None}, INVALID),
+    ("dm_orth_project_fused_f32", {"B": 0}, {"frames": None, "depth": None, "value": _PTR}, INVALID),
+    ("dm_orth_project_fused_f32", {"B": 0}, {"accumulate": 1, "ws": None}, WORKSPACE),
+    # winners / backward: prod first, then B == 0, NULL pointers, the workspace (B frames)
+    ("dm_orth_project_winners_f32", {"reduction": PROD}, {}, UNSUPPORTED),
+    ("dm_orth_project_winners_f32", {"reduction": PROD, "B": 0}, {}, UNSUPPORTED),
+    ("dm_orth_project_winners_f32", {"reduction": 9}, {}, INVALID),
+    ("dm_orth_project_winners_f32", {"B": 0}, {"frames": None, "depth": None, "ws": None}, OK),
+    ("dm_orth_project_winners_f32", {"B": 0}, {"value": _PTR}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"frames": None}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"depth": None}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"ws": None}, WORKSPACE),
+    ("dm_orth_project_winners_f32", {}, {"ws_bytes": -1}, WORKSPACE),
+    ("dm_orth_project_winners_f32", {}, {"value": _PTR}, INVALID),
+    ("dm_orth_project_winners_f32", {"vc": 1}, {}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_winners_f32", {"valid_c": 1}, {}, INVALID),
+    ("dm_orth_project_winners_f32", {"reduction": SUM}, {}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"out": None}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"height_winner": _PTR}, INVALID),
+    ("dm_orth_project_winners_f32", {"vc": 1}, {"value": _PTR, "height_winner": _PTR}, INVALID),
+    ("dm_orth_project_winners_f32", {}, {"winner": None}, OK),
+    ("dm_orth_project_backward_f32", {"reduction": PROD}, {}, UNSUPPORTED),
+    ("dm_orth_project_backward_f32", {"reduction": PROD, "B": 0}, {}, UNSUPPORTED),
+    ("dm_orth_project_backward_f32", {"reduction": 9}, {}, INVALID),
+    ("dm_orth_project_backward_f32", {"B": 0}, {"frames": None, "depth": None, "ws": None}, OK),
+    ("dm_orth_project_backward_f32", {"B": 0}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"frames": None}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"depth": None}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"ws": None}, WORKSPACE),
+    ("dm_orth_project_backward_f32", {}, {"ws_bytes": -1}, WORKSPACE),
+    ("dm_orth_project_backward_f32", {}, {"valid": _PTR}, INVALID),
+    ("dm_orth_project_backward_f32", {"valid_c": 1}, {}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"winner": None}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"grad_value": _PTR}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"grad_height": _PTR}, INVALID),
+    ("dm_orth_project_backward_f32", {"vc": 1}, {"grad_height": _PTR}, INVALID),
+    ("dm_orth_project_backward_f32", {}, {"grad_depth": None}, OK),
+]
+
+
+@pytest.mark.parametrize("name,fields,args,want", _REFUSALS)
+def test_projection_refusals_without_gpu(name, fields, args, want):
+  """Each entry point's status code for each kind of bad argument ("ws_bytes": -1 means one byte
+  less than the call needs)."""
+  from dungeon_maps_amd import _native
+  lib = _native.lib()
+  p = _native.Params()
+  p.B, p.dc, p.vc, p.H, p.W, p.mh, p.mw, p.reduction = 1, 1, 0, 4, 4, 8, 8, MAX
+  for k, v in fields.items():
+    setattr(p, k, v)
+  if name in ("dm_orth_project_winners_f32", "dm_orth_project_backward_f32"):
+    need = p.B * _native.FRAME_FLOATS * 4
+  else:
+    need = lib.dm_orth_project_workspace_bytes(ctypes.byref(p))
+  given = dict.fromkeys(_GIVEN[name], _PTR)
+  given.update(ws=_PTR, ws_bytes=need, accumulate=0, status=None, stream=None)
+  given.update(args)
+  if given["ws_bytes"] == -1:
+    assert need > 0
+    given["ws_bytes"] = need - 1
+  plan = _native.FramesPlan()
+  if name == "dm_orth_project_prepared_f32" and given["plan"] is not None:
+    given["plan"] = ctypes.byref(plan)
+  values = [given.get(a) for a in _ARGS[name]]
+  assert getattr(lib, name)(ctypes.byref(p), *values) == want, lib.dm_last_error()
