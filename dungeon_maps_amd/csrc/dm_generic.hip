@@ -239,6 +239,19 @@ static bool frame_unions(const dm_params& p, const dm_frame* frames_host, std::v
   return covered * 2 <= (size_t)p.B * p.mh * p.mw;
 }
 
+// The value a map starts at.  A NaN fill never changes under max / min (torch_scatter stores only if
+// new > old), but atomic_max_f32 / atomic_min_f32 order bit patterns: a NaN with the sign bit set
+// lies below every number for max, one without it above every number for min.  Such maps start at
+// the NaN those atomics cannot move.
+static float start_value(const dm_params& p) {
+  if (p.fill == p.fill) return p.fill;
+  const uint32_t bits = p.reduction == DM_REDUCE_MAX ? 0x7fffffffu
+                        : p.reduction == DM_REDUCE_MIN ? 0xffffffffu : 0x7fc00000u;
+  float f;
+  memcpy(&f, &bits, sizeof f);
+  return f;
+}
+
 hipError_t run_generic(const dm_params& p, const dm_frame* frames_host, const float* depth,
                        const float* value, const uint8_t* valid, float* out,
                        uint8_t* mask, float* height, void* ws, hipStream_t s) {
@@ -270,7 +283,7 @@ hipError_t run_generic(const dm_params& p, const dm_frame* frames_host, const fl
   }
   if (ue != hipSuccess) return ue;
   hipLaunchKernelGGL(k_fill, dim3(blocks_for(n_out > n_h ? n_out : n_h, 1024, 4096)), dim3(256),
-                     0, s, out, p.fill, n_out, height, -__builtin_inff(), n_h,
+                     0, s, out, start_value(p), n_out, height, -__builtin_inff(), n_h,
                      by_unions ? reinterpret_cast<uint32_t*>(mask) : nullptr,
                      by_unions ? n_out / 4 : (size_t)0);
   if (count)
@@ -298,7 +311,7 @@ hipError_t run_generic_fused(const dm_params& p, const dm_frame* frames_host, co
   const size_t M = (size_t)p.mh * p.mw, oc = p.vc ? p.vc : p.dc;
   const size_t n_out = oc * M;
   if (!accumulate)
-    hipLaunchKernelGGL(k_fill, dim3(blocks_for(n_out, 1024, 4096)), dim3(256), 0, s, out, p.fill,
+    hipLaunchKernelGGL(k_fill, dim3(blocks_for(n_out, 1024, 4096)), dim3(256), 0, s, out, start_value(p),
                        n_out, (float*)nullptr, 0.0f, (size_t)0, (uint32_t*)nullptr, (size_t)0);
   const int N = p.H * p.W;
   dim3 grid((N + 255) / 256, p.dc, p.B);

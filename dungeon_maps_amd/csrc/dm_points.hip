@@ -109,10 +109,18 @@ k_scatter_flat(const float* __restrict__ values, const long long* __restrict__ i
 // mask = changed (vs the constant fill or vs the saved copy); mean division
 __global__ void __launch_bounds__(256)
 k_scatter_finalize(float* __restrict__ canvas, const float* __restrict__ before, float fill,
-                   const float* __restrict__ count, uint8_t* __restrict__ mask, size_t n) {
+                   const float* __restrict__ count, uint8_t* __restrict__ mask, size_t n,
+                   int keep_nan) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float o = canvas[i];
+    // max / min: a NaN cell of the caller's canvas never changes (torch_scatter stores only if
+    // new > old), but the integer atomics move a NaN whose sign bit orders it below (max) or
+    // above (min) the values: put it back
+    if (keep_nan && before && !(before[i] == before[i])) {
+      o = before[i];
+      canvas[i] = o;
+    }
     if (count) {
       const float c = count[i];
       o = o / (c < 1.0f ? 1.0f : c);
@@ -337,8 +345,13 @@ hipError_t run_scatter(const float* values, const long long* index, float* canva
   float* before = nullptr;
   float* count = nullptr;
   float* w = static_cast<float*>(ws);
+  const int keep_nan = reduction == DM_REDUCE_MAX || reduction == DM_REDUCE_MIN;
   if (has_fill) {
-    hipLaunchKernelGGL(k_fill1, dim3(nblocks(n)), dim3(256), 0, s, canvas, fill, n);
+    // a NaN fill starts at the NaN the integer atomics cannot move (see k_scatter_finalize)
+    uint32_t bits = reduction == DM_REDUCE_MIN ? 0xffffffffu : 0x7fffffffu;
+    float start = fill;
+    if (keep_nan && !(fill == fill)) memcpy(&start, &bits, sizeof start);
+    hipLaunchKernelGGL(k_fill1, dim3(nblocks(n)), dim3(256), 0, s, canvas, start, n);
   } else {
     before = w; w += n;
     hipError_t e = hipMemcpyAsync(before, canvas, n * sizeof(float), hipMemcpyDeviceToDevice, s);
@@ -354,7 +367,7 @@ hipError_t run_scatter(const float* values, const long long* index, float* canva
                        M, reduction);
   }
   hipLaunchKernelGGL(k_scatter_finalize, dim3(nblocks(n)), dim3(256), 0, s, canvas, before, fill,
-                     count, mask, n);
+                     count, mask, n, keep_nan);
   return hipGetLastError();
 }
 

@@ -479,7 +479,9 @@ k_window_scatter(ScatterArgs a, const ScatterTables* __restrict__ tables) {
             if (!LEAN) ok[k] = ok[k] && !__builtin_isunordered(xf, zf) && h1 <= a.hmax;
             if (!FAST && !HAS_VALUE) ok[k] = ok[k] && (h2 == h2);
             const float sval = HAS_VALUE ? sv[u][k] : h2;
-            if (HAS_VALUE) ok[k] = ok[k] && (sval == sval);      // NaN never replaces a number
+            // max / min: NaN never replaces a number.  sum / mean: a NaN value makes the cell NaN
+            // and is counted, as torch_scatter's scatter_add / scatter_mean do
+            if (HAS_VALUE && !additive(RED)) ok[k] = ok[k] && (sval == sval);
             // rejected pixels are redirected to a per-lane dummy cell behind the
             // window instead of being branched around: the whole row group stays
             // one basic block the scheduler can interleave
