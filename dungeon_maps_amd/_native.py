@@ -19,6 +19,11 @@ REDUCE_MAX, REDUCE_MIN, REDUCE_SUM, REDUCE_MEAN, REDUCE_PROD = range(5)
 
 FRAME_FLOATS = 32  # sizeof(dm_frame) / 4
 
+# dm_label_dtype (by torch / numpy dtype name), the native label route's class limit, dm_debug_last_label_route
+LABEL_DTYPE_CODE = {"uint8": 0, "int16": 1, "int32": 2, "int64": 3}
+LABEL_NATIVE_MAX_CLASSES = 63
+LABEL_ROUTE_NATIVE, LABEL_ROUTE_COMPAT = 1, 2
+
 
 class Params(ctypes.Structure):
   """dm_params"""
@@ -70,6 +75,16 @@ _SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
         ctypes.c_void_p]),
+    "dm_orth_project_labels_workspace_bytes": (ctypes.c_size_t, [
+        ctypes.POINTER(Params), ctypes.c_int32, ctypes.c_int32]),
+    "dm_orth_project_labels": (ctypes.c_int, [
+        ctypes.POINTER(Params), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "dm_labels_one_hot_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t,
+        ctypes.c_void_p, ctypes.c_void_p]),
+    "dm_debug_last_label_route": (ctypes.c_int, []),
     "dm_orth_project_winners_f32": (ctypes.c_int, [
         ctypes.POINTER(Params), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -94,6 +94,18 @@ k_unpad(const float* __restrict__ src, const uint8_t* __restrict__ src_mask, flo
 
 }  // namespace
 
+// dm_kernels.hpp: the error string and the parameter check for entry points in other translation units
+namespace dm {
+int set_error(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+int validate_params(const dm_params* p) { return check_params(p); }
+}  // namespace dm
+
 extern "C" {
 
 int dm_version(void) { return DM_ABI_VERSION; }

@@ -7,6 +7,11 @@
 
 namespace dm {
 
+// dm_api.hip -- dm_last_error()'s message (returns `code`) and the call-wide parameter check, for entry
+// points that live in other translation units (dm_labels.hip)
+int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int validate_params(const dm_params* p);
+
 // dm_generic.hip -- fill / global-atomic scatter / finalize
 size_t generic_workspace_bytes(const dm_params& p);
 hipError_t run_generic(const dm_params& p, const dm_frame* frames_host, const float* depth,

@@ -292,7 +292,7 @@ def orth_project(
     clip_border: Optional[int], to_global: bool, flip_h: bool = True,
     fill_value: Optional[float] = None, reduction: Optional[Reduction] = None,
     get_height_map: bool = False, device: Optional[torch.device] = None,
-    _validate_args: bool = True
+    _validate_args: bool = True, label_map=None, num_classes: Optional[int] = None
 ) -> Union[Tuple[torch.Tensor, torch.Tensor],
            Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
   """Orthographic projection of depth maps (b, c, h, w) to top-down maps.
@@ -306,7 +306,27 @@ def orth_project(
   One fused HIP launch sequence replaces the reference's ~230 ATen calls:
   unproject, pitch/yaw/translate, truncations, quantisation, scatter-reduce and
   the changed-mask (dm_orth_project_f32).
+
+  Not in the reference: ``label_map`` with ``num_classes`` projects a class-label image to an object
+  map without its one-hot value map.  ``label_map`` is an integer tensor / array (uint8, int16, int32
+  or int64; a CPU int64 numpy array works as it is) of shape (b, 1, h, w) or a lower-rank form of
+  it, matching the one-channel ``depth_map`` -- a simulator's (h, w, 1) / (b, h, w, 1) layout is taken
+  too.  The call returns, bit for bit, what it returns with
+  ``value_map[b, c, y, x] = 1.0 if label_map[b, 0, y, x] == c else 0.0`` for c in [0, num_classes).
+  A label outside [0, num_classes) (negative, a 255 "void") is an all-zero row: the pixel is still a
+  point -- it marks its cell, counts for 'mean', contributes to the height map -- of no class
+  (``one_hot`` would raise there).  Reductions max / min with up to 63 classes run on kernels that
+  never build the value map (one class word per map cell); everything else -- sum / mean / prod,
+  more classes, a fill of -0.0, a call that needs gradients -- expands the labels to the float32
+  one-hot tensor on the device (b * num_classes * h * w * 4 bytes of scratch) in front of the
+  ordinary projection.  ``label_map`` excludes ``value_map``.
   """
+  if label_map is not num_classes:      # (both None on a call without labels: the same object)
+    return _orth_project_labels(
+        depth_map, value_map, valid_map, cam_pose, width_offset, height_offset, cam_pitch, cam_height,
+        map_res, map_width, map_height, focal_x, focal_y, center_x, center_y, trunc_depth_min,
+        trunc_depth_max, trunc_height_max, clip_border, to_global, flip_h, fill_value, reduction,
+        get_height_map, device, label_map, num_classes)
   grad = torch.is_grad_enabled() and _wants_grad(depth_map, value_map, cam_pitch, cam_height) \
       and Reduction(reduction) is not Reduction.prod
   call = _Call(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset, cam_pitch,
@@ -461,6 +481,100 @@ def _orth_project(call, get_height_map, _fuse, _fused_out, _out):
   _launch(call, call.depth, call.value, topdown, mask, height, fused, fmask)
   if _fuse:
     return _to_target(call, topdown, mask, fused, fmask)
+  topdown, mask, height = _to_target(call, topdown, mask, height)
+  return _with_height(topdown, mask, height, get_height_map)
+
+
+# ---------------------------------------------------------------------------
+# orth_project(label_map=, num_classes=): class-label images instead of a one-hot value map
+# (dm_orth_project_labels).  A sibling of the route above; calls without labels never come here.
+# ---------------------------------------------------------------------------
+_LABEL_DTYPES = {torch.uint8: "uint8", torch.int16: "int16", torch.int32: "int32", torch.int64: "int64"}
+
+
+def _label_image(label_map, depth_map, value_map, num_classes):
+  """The checked (b, 1, h, w) label tensor (on the device it came on, its own integer dtype) and its
+  dm_label_dtype code.  Every refusal is a ValueError raised before a GPU is looked for."""
+  if value_map is not None:
+    raise ValueError("`label_map` and `value_map` exclude each other: the labels are the value map")
+  if label_map is None:
+    raise ValueError("`num_classes` was given without a `label_map`")
+  if num_classes is None:
+    raise ValueError("`label_map` needs `num_classes`")
+  if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 1:
+    raise ValueError(f"`num_classes` must be an int >= 1, got {num_classes!r}")
+  labels = label_map if torch.is_tensor(label_map) else utils.to_tensor(label_map)
+  name = _LABEL_DTYPES.get(labels.dtype)
+  if name is None:
+    raise ValueError(f"`label_map` must be uint8, int16, int32 or int64, got {labels.dtype}")
+  depth = depth_map if torch.is_tensor(depth_map) else utils.to_tensor(depth_map)
+  if depth.dim() not in (2, 3, 4) or labels.dim() not in (2, 3, 4):
+    raise ValueError(f"depth_map {tuple(depth.shape)} / label_map {tuple(labels.shape)}: 2 to 4 dimensions")
+  want = tuple(utils.to_4D_image(depth).shape)
+  if want[1] != 1:
+    raise ValueError(f"`label_map` needs a one-channel depth map, got {want[1]} channels")
+  if labels.dim() >= 3 and labels.shape[-1] == 1 and tuple(labels.shape[-3:-1]) == want[2:] \
+      and tuple(utils.to_4D_image(labels).shape) != want:
+    labels = labels.movedim(-1, -3)            # (.., h, w, 1), a simulator's layout
+  if tuple(utils.to_4D_image(labels).shape) != want:
+    raise ValueError(f"label_map {tuple(label_map.shape)} does not match depth_map {tuple(depth.shape)}")
+  return utils.to_4D_image(labels), _native.LABEL_DTYPE_CODE[name]
+
+
+def _one_hot_on_device(labels, code, num_classes) -> torch.Tensor:
+  """(b, num_classes, h, w) float32 one-hot of device labels (dm_labels_one_hot_f32)."""
+  B, _, H, W = labels.shape
+  value = torch.empty((B, num_classes, H, W), dtype=torch.float32, device=labels.device)
+  with _on_device(labels.device):
+    _native.check(_native.lib().dm_labels_one_hot_f32(
+        _ptr(labels), code, num_classes, B, H * W, _ptr(value), _stream_ptr(labels.device)))
+  return value
+
+
+def _launch_labels(call, labels, code, num_classes, topdown, mask, height) -> None:
+  """Enqueue dm_orth_project_labels for ``call`` on the current stream of its GPU."""
+  lib = _native.lib()
+  ws_bytes = int(lib.dm_orth_project_labels_workspace_bytes(ctypes.byref(call.params), code, num_classes))
+  ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=call.dev)
+  _native.check_status()
+  with _on_device(call.dev):
+    _native.check(lib.dm_orth_project_labels(
+        ctypes.byref(call.params), _ptr(call.frames), _ptr(call.depth), _ptr(labels), code, num_classes,
+        _ptr(call.valid), _ptr(topdown), _ptr(mask), _ptr(height), _ptr(ws), ws_bytes,
+        _native.status_ptr(), _stream_ptr(call.dev)))
+
+
+def _orth_project_labels(depth_map, value_map, valid_map, cam_pose, width_offset, height_offset,
+                         cam_pitch, cam_height, map_res, map_width, map_height, focal_x, focal_y,
+                         center_x, center_y, trunc_depth_min, trunc_depth_max, trunc_height_max,
+                         clip_border, to_global, flip_h, fill_value, reduction, get_height_map, device,
+                         label_map, num_classes):
+  labels, code = _label_image(label_map, depth_map, value_map, num_classes)
+  num_classes = int(num_classes)
+  _reduction_code(reduction)
+  grad = torch.is_grad_enabled() and _wants_grad(depth_map, cam_pitch, cam_height) \
+      and Reduction(reduction) is not Reduction.prod
+  args = (valid_map, cam_pose, width_offset, height_offset, cam_pitch, cam_height, map_res, map_width,
+          map_height, focal_x, focal_y, center_x, center_y, trunc_depth_min, trunc_depth_max,
+          trunc_height_max, clip_border, to_global, flip_h, fill_value, reduction, device)
+  if grad:
+    # topdown depends on no differentiable input, the height map does: the existing autograd
+    # Function on the value map, expanded on the device
+    first = depth_map if torch.is_tensor(depth_map) else utils.to_tensor(depth_map)
+    dev = _compute_device(torch.device(device) if device is not None else first.device)
+    value = _one_hot_on_device(labels.to(dev).contiguous(), code, num_classes)
+    return _orth_project_grad(_Call(depth_map, value, *args), cam_pitch, cam_height, get_height_map)
+  # the heights' call: one depth channel, no value map (the label entry point's parameters)
+  call = _Call(depth_map, None, *args)
+  if labels.device != call.dev:
+    labels = labels.to(call.dev)
+  if not labels.is_contiguous():
+    labels = labels.contiguous()
+  p = call.params
+  topdown, mask = _empty_maps((p.B, num_classes, p.mh, p.mw), call.dev)
+  height = torch.empty((p.B, 1, p.mh, p.mw), dtype=torch.float32, device=call.dev) \
+      if get_height_map else None
+  _launch_labels(call, labels, code, num_classes, topdown, mask, height)
   topdown, mask, height = _to_target(call, topdown, mask, height)
   return _with_height(topdown, mask, height, get_height_map)
 

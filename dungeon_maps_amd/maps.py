@@ -605,6 +605,10 @@ def fuse_topdown_maps(*maps: TopdownMap, map_projector: Optional[MapProjector] =
                     map_projector=new_proj, is_height_map=is_height_map)
 
 
+# per-call arguments MapBuilder.plot forwards to orth_project and keeps out of the projector clone
+_LABEL_KWARGS = ("label_map", "num_classes")
+
+
 class MapBuilder:
   """Stateful world-map builder (reference maps.py:2289-2550)."""
 
@@ -637,17 +641,22 @@ class MapBuilder:
   def plot(self, depth_map, value_map=None, valid_map=None, cam_pose=None,
            center_mode: CenterMode = CenterMode.none, **kwargs: Dict[str, Any]) -> TopdownMap:
     """Project a frame to a TopdownMap; ``kwargs`` override the projector's
-    orth_project defaults and are recorded in the returned map's projector."""
+    orth_project defaults and are recorded in the returned map's projector.
+
+    ``label_map=`` with ``num_classes=`` (through ``kwargs``, as in ``step`` and ``reset``: the
+    reference's signatures end in ``**kwargs``) projects a class-label image instead of a one-hot
+    ``value_map``: see ``orth_project``.  They are arguments of this call, not projector settings."""
     cam_pose = get(cam_pose, self.proj.cam_pose, np.zeros(3, dtype=np.float32))
+    labels = {k: kwargs.pop(k) for k in _LABEL_KWARGS if k in kwargs}
     woff, hoff = self._compute_offsets(cam_pose=cam_pose, center_mode=center_mode, **kwargs)
     kwargs["width_offset"], kwargs["height_offset"] = woff, hoff
     kwargs.pop("get_height_map", None)
     topdown, mask, height = self.proj.orth_project(
         depth_map=depth_map, value_map=value_map, valid_map=valid_map, cam_pose=cam_pose,
-        get_height_map=True, **kwargs)
+        get_height_map=True, **kwargs, **labels)
     return TopdownMap(topdown_map=topdown, mask=mask, height_map=height,
                       map_projector=self.proj.clone(cam_pose=cam_pose, **kwargs),
-                      is_height_map=value_map is None)
+                      is_height_map=value_map is None and not labels)
 
   def merge(self, topdown_map: TopdownMap, keep_pose: bool = False,
             fill_value: Optional[float] = None,

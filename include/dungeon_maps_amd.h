@@ -33,6 +33,9 @@
 extern "C" {
 #endif
 
+/* 11 since the backward entry points.  The label entry points (dm_orth_project_labels ...) are additions: no
+ * existing symbol, struct or meaning changed, so the number stays; a binding finds out whether a library
+ * has them by looking the symbols up (the Python binding does so for every declared symbol on load). */
 #define DM_ABI_VERSION 11
 
 typedef enum dm_status {
@@ -196,6 +199,49 @@ int dm_orth_project_flow_f32(const dm_params* p, const dm_frame* frames, const d
                              uint8_t* mask_dev, float* fused_dev, uint8_t* fused_mask_dev,
                              float* grid_dev, void* workspace_dev, size_t workspace_bytes,
                              int32_t* status_dev, void* stream);
+
+/*
+ * Object maps from class-label images (an addition within ABI v11): dm_orth_project_f32 of the one-hot value map
+ *   value[b, c, y, x] = labels[b, 0, y, x] == c ? 1.0f : 0.0f,   c in [0, num_classes)
+ * without that value map -- what the reference's object-map demo builds in front of every call
+ * (demos/object_map/run.py: one_hot -> permute -> float) and orth_project then reads back
+ * (maps.py:127-351).  Results are those of that call bit for bit.
+ *   p            dm_orth_project_f32's parameters with dc == 1 and vc == 0 on entry (the labels ARE the
+ *                value map; the outputs have num_classes channels)
+ *   labels_dev   (B, 1, H, W) integers of type `label_dtype` (dm_label_dtype), never converted or expanded
+ *                on the native route.  A label outside [0, num_classes) -- negative, a 255 "void" -- is an
+ *                all-zero row of the value map: the pixel is still a point (it hits its cell, counts for
+ *                'mean', contributes to the height map), it belongs to no class.
+ *   out_dev      (B, num_classes, mh, mw) f32, mask_dev likewise u8 (0/1)
+ *   height_dev   (B, 1, mh, mw) f32 or NULL: the NINF / max height map (maps.py:332-350)
+ * Two routes, chosen from the parameters alone (dm_debug_last_label_route tells which ran):
+ *   native         reduction max / min, num_classes <= DM_LABEL_NATIVE_MAX_CLASSES, any fill but -0.0, every
+ *                  geometry: one pass over the pixels records the classes seen in each cell (64-bit words,
+ *                  B * mh * mw * 8 bytes of workspace), one pass writes every channel of out and mask
+ *                  from them; the height map is dm_orth_project_f32's heights projection.
+ *   compatibility  everything else: the labels are expanded to the float32 one-hot tensor in the workspace
+ *                  (B * num_classes * H * W * 4 bytes) and dm_orth_project_f32 runs on it.
+ * Same contract as dm_orth_project_f32: enqueues on `stream` only, allocates nothing, outputs fully
+ * written, arguments validated before any HIP call.  Workspace: dm_orth_project_labels_workspace_bytes,
+ * 256-byte aligned.
+ *
+ * dm_labels_one_hot_f32: the expansion on its own -- labels (B, n) -> out_dev (B, num_classes, n) f32 --
+ * for callers that need the value map itself (the Python layer's autograd route).
+ */
+typedef enum dm_label_dtype {
+  DM_LABEL_U8 = 0,
+  DM_LABEL_I16 = 1,
+  DM_LABEL_I32 = 2,
+  DM_LABEL_I64 = 3
+} dm_label_dtype;
+#define DM_LABEL_NATIVE_MAX_CLASSES 63
+size_t dm_orth_project_labels_workspace_bytes(const dm_params* p, int32_t label_dtype, int32_t num_classes);
+int dm_orth_project_labels(const dm_params* p, const dm_frame* frames, const float* depth_dev,
+                           const void* labels_dev, int32_t label_dtype, int32_t num_classes,
+                           const uint8_t* valid_dev, float* out_dev, uint8_t* mask_dev, float* height_dev,
+                           void* workspace_dev, size_t workspace_bytes, int32_t* status_dev, void* stream);
+int dm_labels_one_hot_f32(const void* labels_dev, int32_t label_dtype, int32_t num_classes, int64_t B,
+                          size_t n, float* out_dev, void* stream);
 
 /*
  * Backward of dm_orth_project_f32 (autograd of the reference's chain: unproject -> rotations ->

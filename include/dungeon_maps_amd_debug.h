@@ -72,6 +72,7 @@ int dm_debug_force_bands(int on);
  *                                thread's projections take: 1 non-temporal, 0 the default policy,
  *                                -1 the library's own rule (non-temporal where the call's batch
  *                                fuse follows or the maps exceed what the Infinity Cache keeps);
+ *                                also the map stores of a label call's expansion kernel;
  *                                returns the previous setting.  Same results; lets a measurement
  *                                time a plain call on the kernel variant a fused call launches.
  *   dm_debug_strip_value_list    0: value maps of three channels or more recompute every pixel's cell
@@ -161,6 +162,16 @@ size_t dm_debug_slab_budget(size_t bytes);
  * operation the call enqueues (after its host-side geometry). */
 void dm_debug_record_before_projection(void* event);
 void dm_debug_record_after_projection(void* event);
+
+/*
+ * Test hook: the route the calling thread's most recent label call (dm_orth_project_labels,
+ * dm_labels_one_hot_f32) took: 0 none yet, DM_LABEL_ROUTE_NATIVE the class-set kernels,
+ * DM_LABEL_ROUTE_COMPAT the one-hot expansion in front of dm_orth_project_f32.  The native route's
+ * expansion follows dm_debug_force_nt_fill for the cache policy of its map stores.
+ */
+#define DM_LABEL_ROUTE_NATIVE 1
+#define DM_LABEL_ROUTE_COMPAT 2
+int dm_debug_last_label_route(void);
 
 /*
  * dm_debug_planes: the strip path's compact planes for the groups several strips share (calls of at most four
