@@ -13,13 +13,8 @@ thread_local int g_force_generic = 0;   // dm_debug_force_generic_path (tests)
 thread_local hipEvent_t g_mid_event = nullptr;   // dm_debug_record_after_projection (bench)
 thread_local hipEvent_t g_pre_event = nullptr;   // dm_debug_record_before_projection (bench)
 
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
+using dm::Arena; using dm::check_workspace; using dm::launch_status;
+constexpr auto& fail = dm::set_error;       // (defined below: one body for this file and the other translation units)
 
 int check_params(const dm_params* p) {
   if (!p) return fail(DM_ERR_INVALID_ARGUMENT, "params is NULL");
@@ -52,32 +47,28 @@ int check_inputs(const dm_params* p, const void* value_dev, const void* valid_de
   return DM_OK;
 }
 
-int check_workspace(const void* workspace_dev, size_t workspace_bytes, size_t need) {
-  if (need > workspace_bytes || !workspace_dev)
-    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes, need);
-  return DM_OK;
-}
-
-int launch_status(hipError_t e) {
-  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
-}
-
 // Map widths that are not a multiple of 4 (odd ego-centric maps: 241 x 241 ...): the LDS-windowed
 // path needs 16-byte rows.  Instead of the ~9x slower generic path, the call then projects into
 // maps padded to the next multiple of 4 (workspace) and copies the real columns out: columns
 // are independent, so the kept ones are identical.
-inline bool padded_route(const dm_params& p) {
-  if (p.mw % 4 == 0) return false;
+inline dm_params padded_params(const dm_params& p) {
   dm_params q = p;
   q.mw = (p.mw + 3) & ~3;
-  return dm::window_path_supported(q);
+  return q;
 }
-inline size_t padded_bytes(const dm_params& p) {          // padded out + mask (+ height), 256-aligned
+inline bool padded_route(const dm_params& p) {
+  return p.mw % 4 != 0 && dm::window_path_supported(padded_params(p));
+}
+// workspace of the padded route: padded out | mask | height (value maps) | the window path's own workspace
+struct PaddedWs { float* out; uint8_t* mask; float* height; };
+PaddedWs padded_layout(Arena& a, const dm_params& p) {
   const size_t mw4 = (size_t)((p.mw + 3) & ~3), oc = p.vc ? p.vc : p.dc;
-  const size_t cells = (size_t)p.B * oc * p.mh * mw4, hcells = p.vc ? (size_t)p.B * p.dc * p.mh * mw4 : 0;
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  return up(cells * 4) + up(cells) + up(hcells * 4);
+  const size_t cells = (size_t)p.B * oc * p.mh * mw4;
+  PaddedWs w;
+  w.out = a.take<float>(cells);
+  w.mask = a.take<uint8_t>(cells);
+  w.height = a.take<float>(p.vc ? (size_t)p.B * p.dc * p.mh * mw4 : 0);
+  return w;
 }
 
 __global__ void __launch_bounds__(256)
@@ -94,7 +85,8 @@ k_unpad(const float* __restrict__ src, const uint8_t* __restrict__ src_mask, flo
 
 }  // namespace
 
-// dm_kernels.hpp: the error string and the parameter check for entry points in other translation units
+// dm_kernels.hpp: the error string and the call-wide checks, for this file and for entry points in other
+// translation units
 namespace dm {
 int set_error(int code, const char* fmt, ...) {
   va_list ap;
@@ -104,6 +96,15 @@ int set_error(int code, const char* fmt, ...) {
   return code;
 }
 int validate_params(const dm_params* p) { return check_params(p); }
+int check_workspace(const void* workspace_dev, size_t workspace_bytes, size_t need) {
+  if (need > workspace_bytes || !workspace_dev)
+    return fail(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes, need);
+  return DM_OK;
+}
+int launch_status(hipError_t e) {
+  if (e != hipSuccess) return fail(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
+  return DM_OK;
+}
 }  // namespace dm
 
 extern "C" {
@@ -135,10 +136,10 @@ size_t dm_orth_project_workspace_bytes(const dm_params* p) {
     const size_t w = dm::window_workspace_bytes(*p) + dm::strip_workspace_extra(*p);
     if (w > n) n = w;
   } else if (padded_route(*p)) {
-    dm_params q = *p;
-    q.mw = (p->mw + 3) & ~3;
-    const size_t w = padded_bytes(*p) + dm::window_workspace_bytes(q);
-    if (w > n) n = w;
+    Arena a;
+    padded_layout(a, *p);
+    a.take<unsigned char>(dm::window_workspace_bytes(padded_params(*p)));
+    if (a.used() > n) n = a.used();
   }
   return n;
 }
@@ -173,6 +174,7 @@ static int orth_project_impl(const dm_params* p, const dm_frame* frames, const f
   g_mid_event = nullptr;
   g_pre_event = nullptr;
   bool flowed = false;        // the projection kernel wrote the flow grid
+  Arena ws(workspace_dev, workspace_bytes);
   // after the projection proper: record `mid`, then the batch-fused map and its mask if one was asked for
   auto finish = [&](hipError_t r) {
     if (r == hipSuccess && mid) r = hipEventRecord(mid, s);
@@ -195,22 +197,16 @@ static int orth_project_impl(const dm_params* p, const dm_frame* frames, const f
       e = dm::run_window(pp, frames, depth_dev, value_dev, valid_dev, out_dev, mask_dev,
                          p->vc ? height_dev : nullptr, fused_dev, fused_mask_dev, workspace_dev,
                          workspace_bytes, pre, mid, s, flow_frames, grid_dev, &flowed);
-  } else if (padded_route(*p) && !g_force_generic &&
-           reinterpret_cast<uintptr_t>(workspace_dev) % 256 == 0) {
+  } else if (padded_route(*p) && !g_force_generic && ws.aligned()) {
     // project into padded maps at the head of the workspace, then copy the real columns out
-    dm_params q = *p;
-    q.mw = (p->mw + 3) & ~3;
+    const dm_params q = padded_params(*p);
     const size_t oc = p->vc ? p->vc : p->dc;
-    const size_t cells = (size_t)p->B * oc * p->mh * q.mw;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    unsigned char* base = static_cast<unsigned char*>(workspace_dev);
-    float* out_pad = reinterpret_cast<float*>(base);
-    uint8_t* mask_pad = base + up(cells * 4);
-    float* height_pad = (p->vc && height_dev) ? reinterpret_cast<float*>(base + up(cells * 4) + up(cells))
-                                              : nullptr;
-    const size_t head = padded_bytes(*p);
+    const PaddedWs pad = padded_layout(ws, *p);       // (fits: the size the entry check asked for holds it)
+    float* const out_pad = pad.out;
+    uint8_t* const mask_pad = pad.mask;
+    float* height_pad = (p->vc && height_dev) ? pad.height : nullptr;
     e = dm::run_window(q, frames, depth_dev, value_dev, valid_dev, out_pad, mask_pad, height_pad,
-                       nullptr, nullptr, base + head, workspace_bytes - head, pre, nullptr, s);
+                       nullptr, nullptr, ws.take<unsigned char>(0), ws.rest(), pre, nullptr, s);
     if (e == hipSuccess) {
       const size_t rows = (size_t)p->B * oc * p->mh;
       size_t blocks = (rows * p->mw + 1023) / 1024;

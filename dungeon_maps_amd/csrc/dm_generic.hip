@@ -195,22 +195,23 @@ static hipError_t launch_scatter(const dm_params& p, const View& v, dim3 grid,
   return hipGetLastError();
 }
 
-static inline size_t frames_bytes(const dm_params& p) {
-  return ((size_t)p.B * sizeof(dm_frame) + 255) / 256 * 256;
-}
-
-static inline size_t unions_bytes(const dm_params& p) {
-  return ((size_t)p.B * sizeof(int4) + 255) / 256 * 256;
-}
-
 // workspace: frame table | union windows | per-cell counts (mean only)
+struct GenericWs { dm_frame* frames; int4* unions; float* count; };     // (B) | (B) | (B, oc, mh, mw) or NULL
+static GenericWs generic_layout(Arena& a, const dm_params& p) {
+  const bool mean = p.reduction == DM_REDUCE_MEAN;
+  GenericWs w;
+  w.frames = a.take<dm_frame>(p.B);
+  w.unions = a.take<int4>(p.B);
+  // (an empty region for the other reductions: the size ends on a boundary either way)
+  float* count = a.take<float>(mean ? (size_t)p.B * (p.vc ? p.vc : p.dc) * p.mh * p.mw : 0);
+  w.count = mean ? count : nullptr;
+  return w;
+}
+
 size_t generic_workspace_bytes(const dm_params& p) {
-  size_t n = frames_bytes(p) + unions_bytes(p);
-  if (p.reduction == DM_REDUCE_MEAN) {
-    const size_t oc = p.vc ? p.vc : p.dc;
-    n += (size_t)p.B * oc * p.mh * p.mw * sizeof(float);
-  }
-  return n;
+  Arena a;
+  generic_layout(a, p);
+  return a.used();
 }
 
 // pageable -> device: the bytes have left the host buffer when this returns
@@ -259,24 +260,23 @@ hipError_t run_generic(const dm_params& p, const dm_frame* frames_host, const fl
   const size_t M = (size_t)p.mh * p.mw, oc = p.vc ? p.vc : p.dc;
   const size_t n_out = (size_t)p.B * oc * M;
   const size_t n_h = height ? (size_t)p.B * p.dc * M : 0;
-  unsigned char* base = static_cast<unsigned char*>(ws);
-  const dm_frame* frames = static_cast<const dm_frame*>(ws);
-  const int4* d_unions = reinterpret_cast<const int4*>(base + frames_bytes(p));
-  float* count = p.reduction == DM_REDUCE_MEAN
-      ? reinterpret_cast<float*>(base + frames_bytes(p) + unions_bytes(p)) : nullptr;
+  Arena arena(ws, Arena::kNoLimit);       // (the entry point has checked the size)
+  const GenericWs w = generic_layout(arena, p);
+  float* const count = w.count;
   // frames (+ union windows) in one stream-ordered copy
   thread_local std::vector<int4> unions;
   thread_local std::vector<unsigned char> staging;
   int max_area = 0;
   const bool by_unions = reinterpret_cast<uintptr_t>(out) % 16 == 0 &&
                          reinterpret_cast<uintptr_t>(mask) % 4 == 0 &&
-                         reinterpret_cast<uintptr_t>(ws) % 256 == 0 &&
+                         arena.aligned() &&
                          frame_unions(p, frames_host, unions, &max_area);
   hipError_t ue;
   if (by_unions) {
-    staging.resize(frames_bytes(p) + (size_t)p.B * sizeof(int4));
+    const size_t unions_at = reinterpret_cast<unsigned char*>(w.unions) - reinterpret_cast<unsigned char*>(w.frames);
+    staging.resize(unions_at + (size_t)p.B * sizeof(int4));
     memcpy(staging.data(), frames_host, (size_t)p.B * sizeof(dm_frame));
-    memcpy(staging.data() + frames_bytes(p), unions.data(), (size_t)p.B * sizeof(int4));
+    memcpy(staging.data() + unions_at, unions.data(), (size_t)p.B * sizeof(int4));
     ue = hipMemcpyAsync(ws, staging.data(), staging.size(), hipMemcpyHostToDevice, s);
   } else {
     ue = upload_frames(p, frames_host, ws, s);
@@ -291,13 +291,13 @@ hipError_t run_generic(const dm_params& p, const dm_frame* frames_host, const fl
                        n_out, (float*)nullptr, 0.0f, (size_t)0, (uint32_t*)nullptr, (size_t)0);
   const int N = p.H * p.W;
   dim3 grid((N + 255) / 256, p.dc, p.B);
-  hipError_t e = launch_scatter<false>(p, v, grid, frames, depth, value, valid, out, height,
+  hipError_t e = launch_scatter<false>(p, v, grid, w.frames, depth, value, valid, out, height,
                                        count, s);
   if (e != hipSuccess) return e;
   if (!by_unions) return launch_finalize(out, count, p.fill, mask, n_out, s);
   if (max_area == 0) return hipSuccess;           // no frame reaches its map
   hipLaunchKernelGGL(k_finalize_unions, dim3((unsigned)((max_area / 4 + 255) / 256), (unsigned)(p.B * oc)),
-                     dim3(256), 0, s, out, count, p.fill, mask, d_unions, (int)oc, p.mh, p.mw);
+                     dim3(256), 0, s, out, count, p.fill, mask, w.unions, (int)oc, p.mh, p.mw);
   return hipGetLastError();
 }
 
@@ -306,7 +306,8 @@ hipError_t run_generic_fused(const dm_params& p, const dm_frame* frames_host, co
                              uint8_t* mask, int accumulate, void* ws, hipStream_t s) {
   hipError_t ue = upload_frames(p, frames_host, ws, s);
   if (ue != hipSuccess) return ue;
-  const dm_frame* frames = static_cast<const dm_frame*>(ws);
+  Arena arena(ws, Arena::kNoLimit);
+  const dm_frame* frames = generic_layout(arena, p).frames;      // (the frame table only)
   const View v = make_view(p);
   const size_t M = (size_t)p.mh * p.mw, oc = p.vc ? p.vc : p.dc;
   const size_t n_out = oc * M;

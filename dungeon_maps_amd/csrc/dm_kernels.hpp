@@ -4,13 +4,16 @@
 #include <hip/hip_runtime.h>
 
 #include "dm_pixel.hpp"
+#include "dm_workspace.hpp"
 
 namespace dm {
 
-// dm_api.hip -- dm_last_error()'s message (returns `code`) and the call-wide parameter check, for entry
+// dm_api.hip -- dm_last_error()'s message (returns `code`) and the call-wide checks, for entry
 // points that live in other translation units (dm_labels.hip)
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int validate_params(const dm_params* p);
+int check_workspace(const void* workspace_dev, size_t workspace_bytes, size_t need);
+int launch_status(hipError_t e);
 
 // dm_generic.hip -- fill / global-atomic scatter / finalize
 size_t generic_workspace_bytes(const dm_params& p);

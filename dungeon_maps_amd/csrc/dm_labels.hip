@@ -41,8 +41,6 @@ struct LabelSetArgs {
 };
 static_assert(sizeof(LabelSetArgs) <= 4096, "kernel arguments are limited to 4 KiB");
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // One thread per pixel; grid = (ceil(H*W / 256), 1, frames of this launch).
 template <class T>
 __global__ void __launch_bounds__(256) k_label_sets(LabelSetArgs a) {
@@ -230,6 +228,24 @@ bool nt_expand(const dm_params& p, int C) {
   return (size_t)p.B * C * p.mh * p.mw * 5 > ((size_t)128 << 20);
 }
 
+// Workspace of a call: the route's own regions, then the workspace of the dm_orth_project_f32 call (`inner`)
+//   native:  class words (B, mh, mw) u64 | mask of the height map (B, mh, mw), not returned | heights projection
+//   compat:  one-hot value map (B, C, H, W) f32 | value-map projection
+struct LabelWs { unsigned long long* sets; uint8_t* height_mask; float* one_hot; dm_params inner; };
+LabelWs label_layout(Arena& a, const dm_params& p, int C) {
+  LabelWs w = {};
+  if (native_route(p, C)) {
+    const size_t cells = (size_t)p.B * p.mh * p.mw;
+    w.sets = a.take<unsigned long long>(cells);
+    w.height_mask = a.take<uint8_t>(cells);
+    w.inner = heights_params(p);
+  } else {
+    w.one_hot = a.take<float>((size_t)p.B * C * p.H * p.W);
+    w.inner = one_hot_params(p, C);
+  }
+  return w;
+}
+
 int check_label_call(const dm_params* p, int dtype, int C) {
   int rc = validate_params(p);
   if (rc != DM_OK) return rc;
@@ -255,13 +271,10 @@ int dm_debug_last_label_route(void) { return dm::g_label_route; }
 size_t dm_orth_project_labels_workspace_bytes(const dm_params* p, int32_t label_dtype, int32_t num_classes) {
   using namespace dm;
   if (check_label_call(p, label_dtype, num_classes) != DM_OK) return 0;
-  const size_t M = (size_t)p->mh * p->mw;
-  if (native_route(*p, num_classes)) {
-    const dm_params qh = heights_params(*p);
-    return up256((size_t)p->B * M * 8) + up256((size_t)p->B * M) + dm_orth_project_workspace_bytes(&qh);
-  }
-  const dm_params q = one_hot_params(*p, num_classes);
-  return up256((size_t)p->B * num_classes * p->H * p->W * 4) + dm_orth_project_workspace_bytes(&q);
+  Arena a;
+  const LabelWs w = label_layout(a, *p, num_classes);
+  a.take<unsigned char>(dm_orth_project_workspace_bytes(&w.inner));
+  return a.used();
 }
 
 int dm_labels_one_hot_f32(const void* labels_dev, int32_t label_dtype, int32_t num_classes, int64_t B,
@@ -276,8 +289,7 @@ int dm_labels_one_hot_f32(const void* labels_dev, int32_t label_dtype, int32_t n
   g_label_route = DM_LABEL_ROUTE_COMPAT;
   const hipError_t e = run_one_hot(labels_dev, label_dtype, num_classes, (int)B, (int)n, out_dev,
                                    static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return set_error(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  return DM_OK;
+  return launch_status(e);
 }
 
 int dm_orth_project_labels(const dm_params* p, const dm_frame* frames, const float* depth_dev,
@@ -292,30 +304,27 @@ int dm_orth_project_labels(const dm_params* p, const dm_frame* frames, const flo
     return set_error(DM_ERR_INVALID_ARGUMENT, "frames/depth/labels/out/mask must not be NULL");
   if ((p->valid_c > 0) != (valid_dev != nullptr))
     return set_error(DM_ERR_INVALID_ARGUMENT, "valid pointer and valid_c=%d disagree", p->valid_c);
-  const size_t need = dm_orth_project_labels_workspace_bytes(p, label_dtype, num_classes);
-  if (need > workspace_bytes || !workspace_dev)
-    return set_error(DM_ERR_WORKSPACE_TOO_SMALL, "workspace %zu B < required %zu B", workspace_bytes, need);
-  if (reinterpret_cast<uintptr_t>(workspace_dev) % 256 != 0)
-    return set_error(DM_ERR_INVALID_ARGUMENT, "the workspace must be 256-byte aligned");
+  rc = check_workspace(workspace_dev, workspace_bytes,
+                       dm_orth_project_labels_workspace_bytes(p, label_dtype, num_classes));
+  if (rc != DM_OK) return rc;
+  Arena arena(workspace_dev, workspace_bytes);
+  if (!arena.aligned()) return set_error(DM_ERR_INVALID_ARGUMENT, "the workspace must be 256-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  unsigned char* base = static_cast<unsigned char*>(workspace_dev);
   const int C = num_classes, N = p->H * p->W, M = p->mh * p->mw;
+  const LabelWs w = label_layout(arena, *p, C);
+  void* const inner_ws = arena.take<unsigned char>(0);      // (the rest: the projection's own workspace)
 
   if (!native_route(*p, C)) {
     g_label_route = DM_LABEL_ROUTE_COMPAT;
-    float* one_hot = reinterpret_cast<float*>(base);
-    const size_t head = up256((size_t)p->B * C * N * 4);
-    const hipError_t e = run_one_hot(labels_dev, label_dtype, C, p->B, N, one_hot, s);
-    if (e != hipSuccess) return set_error(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-    const dm_params q = one_hot_params(*p, C);
-    return dm_orth_project_f32(&q, frames, depth_dev, one_hot, valid_dev, out_dev, mask_dev, height_dev,
-                               nullptr, nullptr, base + head, workspace_bytes - head, status_dev, stream);
+    rc = launch_status(run_one_hot(labels_dev, label_dtype, C, p->B, N, w.one_hot, s));
+    if (rc != DM_OK) return rc;
+    return dm_orth_project_f32(&w.inner, frames, depth_dev, w.one_hot, valid_dev, out_dev, mask_dev, height_dev,
+                               nullptr, nullptr, inner_ws, arena.rest(), status_dev, stream);
   }
 
   g_label_route = DM_LABEL_ROUTE_NATIVE;
-  unsigned long long* sets = reinterpret_cast<unsigned long long*>(base);
-  const size_t sets_bytes = (size_t)p->B * M * 8;
-  hipError_t e = hipMemsetAsync(sets, 0, sets_bytes, s);
+  unsigned long long* sets = w.sets;
+  hipError_t e = hipMemsetAsync(sets, 0, (size_t)p->B * M * sizeof(*sets), s);
   LabelSetArgs a;
   a.v = make_view(*p);
   a.valid_c = p->valid_c;
@@ -363,13 +372,9 @@ int dm_orth_project_labels(const dm_params* p, const dm_frame* frames, const flo
     }
     e = hipGetLastError();
   }
-  if (e != hipSuccess) return set_error(DM_ERR_LAUNCH, "HIP launch failed: %s", hipGetErrorString(e));
-  if (!height_dev) return DM_OK;
-  const dm_params qh = heights_params(*p);
-  uint8_t* height_mask = base + up256(sets_bytes);
-  const size_t head = up256(sets_bytes) + up256((size_t)p->B * M);
-  return dm_orth_project_f32(&qh, frames, depth_dev, nullptr, valid_dev, height_dev, height_mask, nullptr,
-                             nullptr, nullptr, base + head, workspace_bytes - head, status_dev, stream);
+  if (e != hipSuccess || !height_dev) return launch_status(e);
+  return dm_orth_project_f32(&w.inner, frames, depth_dev, nullptr, valid_dev, height_dev, w.height_mask, nullptr,
+                             nullptr, nullptr, inner_ws, arena.rest(), status_dev, stream);
 }
 
 }  // extern "C"

@@ -26,8 +26,6 @@ void note_split(int pc, int pr, int pd, int path);     // dm_window.hip (dm_debu
 
 namespace {
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 // Pose-independent plan of a call (the parameters alone).
 struct Plan {
   int P, wp;
@@ -300,9 +298,6 @@ StripKernel pick_value_kernel(bool is_max) {
   return is_max ? k_strip_scatter<kMax, false, true, true, kFromList>
                 : k_strip_scatter<kMin, false, true, true, kFromList>;
 }
-inline size_t pixel_list_bytes(const dm_params& p) {     // (B, P, H, wp) uint16: P * wp <= W + 32 per strip
-  return up256((size_t)p.B * p.H * ((size_t)p.W + 32 * strip::kMaxStrips) * 2);
-}
 thread_local int g_no_value_list = 0;      // dm_debug_strip_value_list(0): every channel recomputes its cells
 thread_local int g_last_info[4] = {0, 0, 0, 0};   // dm_debug_last_strip_info
 thread_local size_t g_strip_slab_budget = 0;    // dm_debug_strip_slab_budget: bytes of slabs per channel group (0: all there is)
@@ -311,43 +306,30 @@ inline bool wants_pixel_list(const dm_params& p) { return list_shape(p) && !g_no
 
 // Workspace of the strip path:
 //   [frame tables: wins (B, 8), unions (B), list counts (B, 8) | shared-group lists (B, P, seg_cap) |
-//    slabs ... | pixel list]
+//    slabs ... | scratch mask of the height pass | pixel list]
 // The tables are written by the scatter kernel for the kernels behind it; nothing is staged
 // from the host.  seg_cap = slab_cells / 4 (a strip lists at most the groups of its window).
-inline size_t tables_bytes(const dm_params& p) {
-  return up256((size_t)p.B * strip::kMaxStrips * sizeof(Win16)) + up256((size_t)p.B * sizeof(Win16)) +
-         up256((size_t)p.B * strip::kMaxStrips * sizeof(int));
-}
-inline size_t lists_bytes(const dm_params& p, int P, int slab_cells) {
-  return up256((size_t)p.B * P * (size_t)(slab_cells / 4) * sizeof(uint32_t));
-}
-// (from the parameters alone: as many strips and as large windows as LDS can hold)
-inline size_t lists_bytes_bound(const dm_params& p) {
-  return lists_bytes(p, strip::kMaxStrips, kMaxLdsBytes / 4);
-}
-
+// The slabs get what is left between the lists and the regions taken from the tail.
 struct Layout {
   FrameTables t;
   float* slabs;
   size_t slab_bytes;
+  uint8_t* scratch_mask;      // value maps with a height map: the mask of the heights pass, not returned (or NULL)
   uint16_t* pixel_list;       // value maps of many channels: the pixels' cells (or NULL)
 };
 
-bool carve(const dm_params& p, int P, int slab_cells, void* ws, size_t ws_bytes, Layout& l) {
-  if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return false;
-  ws_bytes = ws_bytes / 256 * 256;
-  const size_t lb = list_shape(p) ? pixel_list_bytes(p) : 0;
-  const size_t head = tables_bytes(p) + lists_bytes(p, P, slab_cells);
-  if (ws_bytes < head + 256 + lb) return false;
-  unsigned char* base = static_cast<unsigned char*>(ws);
-  l.t.wins = reinterpret_cast<Win16*>(base); base += up256((size_t)p.B * strip::kMaxStrips * sizeof(Win16));
-  l.t.unions = reinterpret_cast<Win16*>(base); base += up256((size_t)p.B * sizeof(Win16));
-  l.t.counts = reinterpret_cast<int*>(base); base += up256((size_t)p.B * strip::kMaxStrips * sizeof(int));
-  l.t.list = reinterpret_cast<uint32_t*>(base); base += lists_bytes(p, P, slab_cells);
-  l.slabs = reinterpret_cast<float*>(base);
-  l.slab_bytes = ws_bytes - head - lb;
-  l.pixel_list = lb ? reinterpret_cast<uint16_t*>(static_cast<unsigned char*>(ws) + ws_bytes - lb) : nullptr;
-  return true;
+Layout strip_layout(Arena& a, const dm_params& p, int P, int slab_cells, bool with_height) {
+  Layout l;
+  l.t.wins = a.take<Win16>((size_t)p.B * strip::kMaxStrips);
+  l.t.unions = a.take<Win16>(p.B);
+  l.t.counts = a.take<int>((size_t)p.B * strip::kMaxStrips);
+  l.t.list = a.take<uint32_t>((size_t)p.B * P * (size_t)(slab_cells / 4));
+  // (B, P, H, wp) uint16: P * wp <= W + 32 per strip
+  l.pixel_list = list_shape(p) ? a.take_tail<uint16_t>((size_t)p.B * p.H * ((size_t)p.W + 32 * strip::kMaxStrips)) : nullptr;
+  l.scratch_mask = with_height ? a.take_tail<uint8_t>((size_t)p.B * p.dc * p.mh * p.mw) : nullptr;
+  l.slabs = a.take<float>(0);
+  l.slab_bytes = a.rest();
+  return l;
 }
 
 template <class K, class... Args>
@@ -557,7 +539,11 @@ size_t strip_workspace_extra(const dm_params& p) {
     more_slabs = per_channel * (size_t)p.vc;
     if (more_slabs > ((size_t)2 << 30)) more_slabs = (size_t)2 << 30;
   }
-  return tables_bytes(p) + lists_bytes_bound(p) + 512 + more_slabs + (list_shape(p) ? pixel_list_bytes(p) : 0);
+  // (from the parameters alone: as many strips and as large windows as LDS can hold, and 512 bytes of slack)
+  Arena a;
+  strip_layout(a, p, strip::kMaxStrips, kMaxLdsBytes / 4, false);
+  a.take<unsigned char>(512 + more_slabs);
+  return a.used();
 }
 
 namespace {
@@ -619,29 +605,28 @@ bool aligned_for_strips(const float* depth, const float* value, const uint8_t* v
 
 // Does the workspace hold what the call needs?  (nothing may be enqueued before the answer is yes)
 bool workspace_fits(const dm_params& p, const Plan& plan, const Rig& rg, bool with_height, void* ws,
-                    size_t ws_bytes, Layout& l, size_t& hm) {
-  if (!carve(p, plan.P, rg.slab_stride, ws, ws_bytes, l)) return false;
-  hm = with_height ? up256((size_t)p.B * p.dc * p.mh * p.mw) : 0;
-  return l.slab_bytes >= hm + (size_t)p.B * plan.P * rg.slab_stride * 4;
+                    size_t ws_bytes, Layout& l) {
+  Arena a(ws, ws_bytes);
+  l = strip_layout(a, p, plan.P, rg.slab_stride, with_height);
+  return a.aligned() && a.ok() && l.slab_bytes >= (size_t)p.B * plan.P * rg.slab_stride * 4;
 }
 
 // The launch sequence proper: nothing here depends on the poses but the kernel arguments (graph
 // capturable: a captured launch replays the poses it was captured with, or reads them from the
 // device buffer of prepared frames).
 hipError_t launch_strips(const dm_params& p, const Plan& plan, const Rig& rg, const PoseSource& poses,
-                         const Layout& l, size_t hm, const float* depth, const float* value,
+                         const Layout& l, const float* depth, const float* value,
                          const uint8_t* valid, float* out, uint8_t* mask, float* height, float* fused,
                          uint8_t* fused_mask, int* status, hipEvent_t after_projection, hipStream_t s) {
   const int oc_total = p.vc ? p.vc : p.dc;
   const bool is_max = p.reduction == DM_REDUCE_MAX;
   g_last_info[0] = g_last_info[1] = g_last_info[2] = g_last_info[3] = 0;
   hipError_t e = strip_pass(p, plan, rg, poses, l, depth, value, valid, out, mask, oc_total, p.fill, is_max,
-                            l.slab_bytes - hm, fused != nullptr, status, s);
+                            l.slab_bytes, fused != nullptr, status, s);
   if (e != hipSuccess) return e;
   if (height && value) {      // maps.py:332-350: second projection of the heights, NINF fill, max
-    uint8_t* scratch_mask = reinterpret_cast<uint8_t*>(l.slabs) + l.slab_bytes - hm;   // (tail of the slab region)
-    e = strip_pass(p, plan, rg, poses, l, depth, nullptr, valid, height, scratch_mask, p.dc, -INFINITY, true,
-                   l.slab_bytes - hm, false, status, s);
+    e = strip_pass(p, plan, rg, poses, l, depth, nullptr, valid, height, l.scratch_mask, p.dc, -INFINITY, true,
+                   l.slab_bytes, false, status, s);
     if (e != hipSuccess) return e;
   }
   if (after_projection) {
@@ -649,14 +634,9 @@ hipError_t launch_strips(const dm_params& p, const Plan& plan, const Rig& rg, co
     if (e != hipSuccess) return e;
   }
   if (fused) {
-    FuseArgs fa;
-    fa.B = p.B; fa.b0 = 0; fa.accumulate = 0;
-    fa.dc = oc_total; fa.mh = p.mh; fa.mw = p.mw; fa.fill = p.fill;
-    fa.unions = l.t.unions; fa.maps = out; fa.fused = fused; fa.fused_mask = fused_mask;
-    const dim3 g((unsigned)(((size_t)p.mh * p.mw / 4 + kUnionGroups - 1) / kUnionGroups), oc_total);
-    const dim3 blk(kUnionGroups * kUnionLanes);
-    e = is_max ? launch(k_fuse_unions<true>, g, blk, 0, s, fa)
-               : launch(k_fuse_unions<false>, g, blk, 0, s, fa);
+    const FuseLaunch f = fuse_unions_launch(p, oc_total, l.t.unions, out, fused, fused_mask);
+    e = is_max ? launch(k_fuse_unions<true>, f.grid, f.block, 0, s, f.args)
+               : launch(k_fuse_unions<false>, f.grid, f.block, 0, s, f.args);
     if (e != hipSuccess) return e;
   }
   note_split(plan.P, 1, 1, 2);
@@ -689,19 +669,21 @@ hipError_t run_strip(const dm_params& p, const dm_frame* frames_host, const floa
   const Plan* plan = plan_and_rig(p, pitch4, magnitude, &rg);
   if (!plan) return hipErrorNotSupported;
   Layout l;
-  size_t hm = 0;
-  if (!workspace_fits(p, *plan, *rg, height && value, ws, ws_bytes, l, hm)) return hipErrorNotSupported;
+  if (!workspace_fits(p, *plan, *rg, height && value, ws, ws_bytes, l)) return hipErrorNotSupported;
   if (before_projection) {
     const hipError_t e = hipEventRecord(before_projection, s);
     if (e != hipSuccess) return e;
   }
   const PoseSource poses = {frames_host, nullptr, p.to_global != 0};
-  return launch_strips(p, *plan, *rg, poses, l, hm, depth, value, valid, out, mask, height, fused, fused_mask,
+  return launch_strips(p, *plan, *rg, poses, l, depth, value, valid, out, mask, height, fused, fused_mask,
                        status, after_projection, s);
 }
 
+// A prepared batch's device buffer: (B) pose records, whole 256-byte units.
+static inline size_t pose_buffer_bytes(int B) { return Arena::round_up((size_t)B * sizeof(StripPose)); }
+
 size_t strip_prepared_bytes(const dm_params& p) {
-  return starting_plan(p, true) ? up256((size_t)p.B * sizeof(StripPose)) : 0;
+  return starting_plan(p, true) ? pose_buffer_bytes(p.B) : 0;
 }
 
 // dm_frames_prepare_f32: validate the batch's camera state, size the launches (the plan) and --
@@ -717,7 +699,7 @@ hipError_t strip_prepare(const dm_params& p, const dm_frame* frames_host, void* 
   const Rig* rg = nullptr;
   const Plan* plan = plan_and_rig(p, pitch4, magnitude, &rg, true);
   if (!plan) return hipErrorNotSupported;
-  if (reinterpret_cast<uintptr_t>(prepared_dev) % 256 != 0 || prepared_size < up256((size_t)p.B * sizeof(StripPose)))
+  if (!Arena(prepared_dev, prepared_size).aligned() || prepared_size < pose_buffer_bytes(p.B))
     return hipErrorInvalidValue;
   const dm_frames_plan fp = plan_of(*plan, *rg, quantised_magnitude(magnitude));
   if (must_match && memcmp(must_match, &fp, sizeof(fp)) != 0) return hipErrorInvalidConfiguration;
@@ -753,14 +735,13 @@ hipError_t run_strip_prepared(const dm_params& p, const dm_frames_plan& fp, cons
       rg->max_union != fp.max_union_cells || rg->slack != fp.slack_cells)
     return hipErrorNotSupported;
   Layout l;
-  size_t hm = 0;
-  if (!workspace_fits(p, *plan, *rg, height && value, ws, ws_bytes, l, hm)) return hipErrorNotSupported;
+  if (!workspace_fits(p, *plan, *rg, height && value, ws, ws_bytes, l)) return hipErrorNotSupported;
   if (before_projection) {
     const hipError_t e = hipEventRecord(before_projection, s);
     if (e != hipSuccess) return e;
   }
   const PoseSource poses = {nullptr, static_cast<const float*>(prepared_dev), p.to_global != 0};
-  return launch_strips(p, *plan, *rg, poses, l, hm, depth, value, valid, out, mask, height, fused, fused_mask,
+  return launch_strips(p, *plan, *rg, poses, l, depth, value, valid, out, mask, height, fused, fused_mask,
                        status, after_projection, s);
 }
 
@@ -896,6 +877,17 @@ FusedKernel pick_fused_kernel(bool is_max, bool has_valid, bool lean, bool defer
   return table[is_max ? 1 : 0][has_valid ? 1 : (lean ? (defer ? 3 : 2) : 0)];
 }
 
+// Workspace of the fused route: the windows of the groups' strips (G, P) | their per-row spans (G, P, rows) |
+// one slab per group of frames, channel and strip (G, dc, P, slab).
+struct FusedLayout { Win16* wins; uint32_t* spans; float* slabs; };
+FusedLayout fused_layout(Arena& a, int G, int P, int rows, int dc, int slab) {
+  FusedLayout l;
+  l.wins = a.take<Win16>((size_t)G * P);
+  l.spans = a.take<uint32_t>((size_t)G * P * rows);
+  l.slabs = a.take<float>((size_t)G * dc * P * slab);
+  return l;
+}
+
 thread_local int g_fused_force[2] = {0, 0};        // dm_debug_force_fused_split: {strip width, frames per group}
 thread_local int g_last_fused[4] = {0, 0, 0, 0};   // dm_debug_last_fused_split: {strip width, strips, frames per group, groups}
 
@@ -909,7 +901,7 @@ hipError_t run_strip_fused(const dm_params& p, const dm_frame* frames_host, cons
   if (g_force_legacy || p.vc != 0 || p.B < 1 || p.B > 65535) return hipErrorNotSupported;
   if (reinterpret_cast<uintptr_t>(depth) % 16 != 0 || reinterpret_cast<uintptr_t>(valid) % 4 != 0 ||
       reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(mask) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(ws) % 256 != 0)
+      !Arena(ws, ws_bytes).aligned())
     return hipErrorNotSupported;
   if ((int64_t)p.H * p.W >= (1ll << 28) || (int64_t)kFusedMaxGroup * p.dc * p.H >= (1 << 23) || p.W >= (1 << 23) ||
       (int64_t)kFusedMaxGroup * p.dc * p.H * p.W * 4 >= (1ll << 31))
@@ -934,8 +926,8 @@ hipError_t run_strip_fused(const dm_params& p, const dm_frame* frames_host, cons
   // per CU of it; a candidate is feasible when the windows of its groups (one frame's bound widened
   // by how far the group's poses are apart) fit in LDS and its slabs in the workspace.  Cost: the
   // scatter's waves of workgroups + the fuse kernel's slab traffic.
-  struct Cand { int wp, F; const FusedBound* fb; int slab, rows; double cost; };
-  Cand best = {0, 0, nullptr, 0, 0, 1e30};
+  struct Cand { int wp, F; const FusedBound* fb; int slab, rows; double cost; FusedLayout l; };
+  Cand best = {0, 0, nullptr, 0, 0, 1e30, {}};
   const int kWave = 256;
   for (int F = kFusedMaxGroup; F >= 1; F >>= 1) {
     if (g_fused_force[1] && F != g_fused_force[1]) continue;
@@ -966,14 +958,14 @@ hipError_t run_strip_fused(const dm_params& p, const dm_frame* frames_host, cons
     int rows = fb->h_max + 2 * m;                       // the group window's height
     rows = ((rows < p.mh ? rows : p.mh) + 3) & ~3;
     if (fused_lds_bytes(slab, p.H, rows) > (size_t)kMaxLdsBytes) continue;
-    const size_t need = up256((size_t)G * fb->P * sizeof(Win16)) + up256((size_t)G * fb->P * rows * 4) +
-                        (size_t)G * p.dc * fb->P * slab * 4;
-    if (need > ws_bytes) continue;
+    Arena a(ws, ws_bytes);
+    const FusedLayout l = fused_layout(a, G, fb->P, rows, p.dc, slab);
+    if (!a.ok()) continue;
     const int wgs = fb->P * p.dc * G;
     const double waves = (double)((wgs + kWave - 1) / kWave);
     const double pixels = (double)wp * p.H * F;
     const double cost = waves * (5.0 + pixels * 2.4e-4) + 2.0 + (double)wgs * slab * 4.0 / 3.0e6;
-    if (cost < best.cost) best = Cand{wp, F, fb, slab, rows, cost};
+    if (cost < best.cost) best = Cand{wp, F, fb, slab, rows, cost, l};
   }
   if (!best.fb) return hipErrorNotSupported;
   const FusedBound& fb = *best.fb;
@@ -1009,9 +1001,7 @@ hipError_t run_strip_fused(const dm_params& p, const dm_frame* frames_host, cons
   const FusedKernel kfn = pick_fused_kernel(is_max, valid != nullptr, fb.lean, defer);
   hipError_t e = raise_lds_limit(reinterpret_cast<const void*>(kfn));
   if (e != hipSuccess) return e;
-  Win16* wins = static_cast<Win16*>(ws);
-  uint32_t* spans = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(ws) + up256((size_t)G * fb.P * sizeof(Win16)));
-  float* slabs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(spans) + up256((size_t)G * fb.P * best.rows * 4));
+  const FusedLayout& l = best.l;
   thread_local FusedArgs fa;
   memset(&fa, 0, offsetof(FusedArgs, poses));
   fa.W = p.W; fa.H = p.H; fa.clip = p.clip_border > 0 ? p.clip_border : 0; fa.flip_h = p.flip_h != 0;
@@ -1024,7 +1014,7 @@ hipError_t run_strip_fused(const dm_params& p, const dm_frame* frames_host, cons
   fa.dc = p.dc; fa.valid_c = p.valid_c; fa.slab_stride = best.slab; fa.max_rows = best.rows; fa.mh = p.mh; fa.mw = p.mw;
   fa.fill = p.fill; fa.cam_h = frames_host[0].cam_height;
   fa.inv = fb.inv; fa.reach = fb.reach; fa.g0 = fb.g0; fa.g1 = fb.g1; fa.cone_ok = 1;
-  fa.slabs = slabs; fa.wins = wins; fa.spans = spans; fa.status = status;
+  fa.slabs = l.slabs; fa.wins = l.wins; fa.spans = l.spans; fa.status = status;
 #ifdef DM_STAMPS
   fa.stamps = g_stamp_buffer;
 #endif
@@ -1051,8 +1041,8 @@ hipError_t run_strip_fused(const dm_params& p, const dm_frame* frames_host, cons
   fw.nwin = G * fb.P; fw.b0 = 0; fw.nparts = fb.P; fw.oc = p.dc; fw.ch0 = 0; fw.oc_total = p.dc;
   fw.mh = p.mh; fw.mw = p.mw; fw.slab_stride = best.slab; fw.accumulate = accumulate; fw.fill = p.fill;
   fw.gx0 = gx0; fw.gz0 = gz0; fw.gx1 = gx1; fw.gz1 = gz1;
-  fw.wins = wins; fw.slabs = slabs; fw.fused = out; fw.fused_mask = mask;
-  fw.spans = spans; fw.span_rows = best.rows;
+  fw.wins = l.wins; fw.slabs = l.slabs; fw.fused = out; fw.fused_mask = mask;
+  fw.spans = l.spans; fw.span_rows = best.rows;
   const int bw4 = (gx1 - gx0) / 4;
   const int heavy = gx1 > gx0 ? ((bw4 + kFuseGroups - 1) / kFuseGroups) * (gz1 - gz0) : 0;
   const int per_fill_block = kFuseGroups * kFuseLanes * 8;

@@ -66,11 +66,25 @@ static int frames_per_chunk(int nparts) {
   return chunk > kChunkFrames ? kChunkFrames : chunk;
 }
 
-static size_t geometry_bytes(int B, int nparts) {
+// Workspace of the window path: [part windows (B, nparts) | union windows (B) | scatter tables, one per
+// chunk of frames | flow records (B) | slabs ... | scratch mask of the height pass].  The slabs get what
+// is left (Arena::rest); the scratch mask is taken from the tail when the height pass runs.
+struct Geometry {
+  Win16* g_wins;                // device copies of the part and union windows
+  Win16* g_unions;
+  const ScatterTables* d_tables;  // one per chunk of frames, filled by ONE stream-ordered copy
+  FlowRec* d_flow;              // (B) flow records (written only by a fused flow call: dm_orth_project_flow_f32)
+  float* slabs;
+};
+static Geometry window_layout(Arena& a, int B, int nparts) {
   const int chunk = frames_per_chunk(nparts);
-  return align_up((size_t)B * nparts * sizeof(Win16), 256) + align_up((size_t)B * sizeof(Win16), 256) +
-         align_up((size_t)((B + chunk - 1) / chunk) * sizeof(ScatterTables), 256) +
-         align_up((size_t)B * sizeof(FlowRec), 256);       // (fused ego-motion flow: dm_orth_project_flow_f32)
+  Geometry g;
+  g.g_wins = a.take<Win16>((size_t)B * nparts);
+  g.g_unions = a.take<Win16>(B);
+  g.d_tables = a.take<ScatterTables>((B + chunk - 1) / chunk);
+  g.d_flow = a.take<FlowRec>(B);
+  g.slabs = a.take<float>(0);
+  return g;
 }
 
 static constexpr size_t kSlabBudget = (size_t)256 << 20;   // slab bytes per channel group
@@ -88,25 +102,24 @@ size_t window_workspace_bytes(const dm_params& p) {
   const size_t one = (size_t)p.B * np * align_up(cap, 4) * 4;     // one channel of every frame
   size_t slabs = one * oc;
   if (slabs > kSlabBudget) slabs = one > kSlabBudget ? one : kSlabBudget;
-  const size_t height_mask = p.vc ? align_up((size_t)p.B * p.dc * p.mh * p.mw, 256) : 0;
-  return geometry_bytes(p.B, kMaxParts) + slabs + height_mask;
+  Arena a;
+  window_layout(a, p.B, kMaxParts);
+  a.take<unsigned char>(slabs);
+  if (p.vc) a.take_tail<uint8_t>((size_t)p.B * p.dc * p.mh * p.mw);
+  return a.used();
 }
 
 namespace {
 
 thread_local size_t g_slab_budget = 0;             // dm_debug_slab_budget (0: no cap)
 
-struct Staged {                 // what run_window keeps between its passes
+struct Staged : Geometry {      // what run_window keeps between its passes
   Parts parts;
   int nparts, slab_stride, max_union;
   int max_tiles;                // k_window_merge_tiled blocks of the largest union window
   int gx0, gz0, gx1, gz1;       // bounding box of all union windows (empty: gx1 <= gx0)
-  Win16* g_wins;                // device copies (workspace head)
-  Win16* g_unions;
-  const ScatterTables* d_tables;  // one per chunk of frames: workspace, filled by ONE stream-ordered copy
-  FlowRec* d_flow;              // (B) flow records, behind the tables (written only by a fused flow call)
+  Arena arena;                  // the workspace with the geometry taken: rest() is the slab region
   int chunk;                    // frames per chunk
-  size_t geom_bytes;
   bool fast, fast_div;
   float res_inv, fx_inv, fy_inv;
   const FrameRec* frames;       // (B)            host, thread-local storage
@@ -369,9 +382,10 @@ bool banded_split_pays(const dm_params& p, const Parts& parts, int nparts, int m
 // hipErrorNotSupported when the windows cannot be made to fit in LDS (the caller then
 // takes the generic path); nothing has been enqueued in that case.
 hipError_t stage_windows(const dm_params& p, const dm_frame* frames_host, void* ws,
-                         size_t ws_bytes, Staged& st, size_t& slab_bytes, hipStream_t s,
+                         size_t ws_bytes, Staged& st, hipStream_t s,
                          hipEvent_t before = nullptr) {
-  if (reinterpret_cast<uintptr_t>(ws) % 256 != 0) return hipErrorNotSupported;
+  st.arena = Arena(ws, ws_bytes);
+  if (!st.arena.aligned()) return hipErrorNotSupported;
   thread_local std::vector<FrameRec> recs;
   thread_local std::vector<Win16> wins;      // (B, nparts) then (B) unions
   // more, narrower parts until every window fits in LDS; when splitting the image does not
@@ -480,9 +494,10 @@ hipError_t stage_windows(const dm_params& p, const dm_frame* frames_host, void* 
         Parts c = c0;
         c.geo = geo;
         if (evaluate(c)) {
-          const size_t geom = geometry_bytes(p.B, st.nparts);
+          Arena probe = st.arena;
+          window_layout(probe, p.B, st.nparts);
           fits = c.pd == 1 || g_force_bands ||
-                 banded_split_pays(p, c, st.nparts, max_area * planes, ws_bytes > geom ? ws_bytes - geom : 0);
+                 banded_split_pays(p, c, st.nparts, max_area * planes, probe.rest());
           done = true;    // splits of more parts cost more still
         }
       }
@@ -500,21 +515,9 @@ hipError_t stage_windows(const dm_params& p, const dm_frame* frames_host, void* 
   g_last_split[0] = st.parts.pc; g_last_split[1] = st.parts.pr; g_last_split[2] = st.parts.pd;
   g_last_path = 1;
   st.slab_stride = (int)align_up((size_t)(max_area > 0 ? max_area : 4), 4) * planes;
-  st.geom_bytes = geometry_bytes(p.B, st.nparts);
-  if (ws_bytes < st.geom_bytes + (size_t)p.B * st.nparts * st.slab_stride * 4)
+  static_cast<Geometry&>(st) = window_layout(st.arena, p.B, st.nparts);
+  if (st.arena.rest() < (size_t)p.B * st.nparts * st.slab_stride * 4)
     return hipErrorOutOfMemory;       // run_window then takes the frames in two halves
-  slab_bytes = ws_bytes - st.geom_bytes;
-  {
-    unsigned char* base = static_cast<unsigned char*>(ws);
-    st.g_wins = reinterpret_cast<Win16*>(base);
-    base += align_up((size_t)p.B * st.nparts * sizeof(Win16), 256);
-    st.g_unions = reinterpret_cast<Win16*>(base);
-    base += align_up((size_t)p.B * sizeof(Win16), 256);
-    st.d_tables = reinterpret_cast<const ScatterTables*>(base);
-    const int chunk_now = frames_per_chunk(st.nparts);
-    base += align_up((size_t)((p.B + chunk_now - 1) / chunk_now) * sizeof(ScatterTables), 256);
-    st.d_flow = reinterpret_cast<FlowRec*>(base);
-  }
 
   recs.resize(p.B);
   for (int b = 0; b < p.B; ++b) {
@@ -586,7 +589,6 @@ hipError_t run_window(const dm_params& p, const dm_frame* frames_host, const flo
       reinterpret_cast<uintptr_t>(height) % 16 != 0)
     return hipErrorNotSupported;
   Staged st;
-  size_t slab_bytes = 0;
 #ifdef DM_HOST_TIMING
   using clk = std::chrono::steady_clock;
   thread_local double acc_t[4] = {0, 0, 0, 0};
@@ -602,7 +604,7 @@ hipError_t run_window(const dm_params& p, const dm_frame* frames_host, const flo
   }
   hipError_t e = shape.halve && !fused && p.B >= 2
                      ? hipErrorOutOfMemory
-                     : stage_windows(p, frames_host, ws, ws_bytes, st, slab_bytes, s, before_projection);
+                     : stage_windows(p, frames_host, ws, ws_bytes, st, s, before_projection);
   if (e == hipErrorOutOfMemory) {
     // many parts of large windows (fine resolution): the slabs of all frames do not fit the
     // workspace.  Frames are independent, so they go through in two halves.
@@ -629,10 +631,6 @@ hipError_t run_window(const dm_params& p, const dm_frame* frames_host, const flo
 #ifdef DM_HOST_TIMING
   const auto t_1 = clk::now();
 #endif
-  unsigned char* base = static_cast<unsigned char*>(ws);
-  float* slabs = reinterpret_cast<float*>(base + st.geom_bytes);
-
-  const bool is_max = p.reduction == DM_REDUCE_MAX;
   const int red = p.reduction == DM_REDUCE_MAX   ? kMax
                   : p.reduction == DM_REDUCE_MIN ? kMin
                   : p.reduction == DM_REDUCE_SUM ? kSum
@@ -655,19 +653,18 @@ hipError_t run_window(const dm_params& p, const dm_frame* frames_host, const flo
     flow_grid = nullptr;
   }
   bool flowed = false;
-  e = window_pass(p, st, slabs, depth, value, valid, out, mask, oc_total, p.fill, red,
-                  slab_bytes, s, nullptr, nullptr, 0, flow_grid, &flowed,
+  e = window_pass(p, st, st.slabs, depth, value, valid, out, mask, oc_total, p.fill, red,
+                  st.arena.rest(), s, nullptr, nullptr, 0, flow_grid, &flowed,
                   /*depth_read_again=*/flow_wanted || (height && value));
   if (e != hipSuccess) return e;
   if (flow_done) *flow_done = flowed;
   g_last_flow_fused = flowed ? 1 : 0;
   if (height && value) {      // maps.py:332-350: second projection, NINF fill, max
     // its mask is not returned (maps.py:340): it goes to scratch at the workspace tail
-    const size_t hm = (size_t)p.B * p.dc * p.mh * p.mw;
-    if (slab_bytes < hm + (size_t)p.B * st.nparts * st.slab_stride * 4) return hipErrorNotSupported;
-    uint8_t* scratch_mask = base + ws_bytes - hm;
-    e = window_pass(p, st, slabs, depth, nullptr, valid, height, scratch_mask, p.dc, -INFINITY, kMax,
-                    slab_bytes - hm, s);
+    uint8_t* scratch_mask = st.arena.take_tail<uint8_t>((size_t)p.B * p.dc * p.mh * p.mw);
+    if (st.arena.rest() < (size_t)p.B * st.nparts * st.slab_stride * 4) return hipErrorNotSupported;
+    e = window_pass(p, st, st.slabs, depth, nullptr, valid, height, scratch_mask, p.dc, -INFINITY, kMax,
+                    st.arena.rest(), s);
     if (e != hipSuccess) return e;
   }
   if (after_projection) {
@@ -678,14 +675,9 @@ hipError_t run_window(const dm_params& p, const dm_frame* frames_host, const flo
   const auto t_2 = clk::now();
 #endif
   if (fused) {
-    FuseArgs fa;
-    fa.B = p.B; fa.b0 = 0; fa.accumulate = 0;
-    fa.dc = oc_total; fa.mh = p.mh; fa.mw = p.mw; fa.fill = p.fill;
-    fa.unions = st.g_unions; fa.maps = out; fa.fused = fused; fa.fused_mask = fused_mask;
-    const dim3 g((unsigned)(((size_t)p.mh * p.mw / 4 + kUnionGroups - 1) / kUnionGroups), oc_total);
-    const dim3 blk(kUnionGroups * kUnionLanes);
-    e = is_max ? launch(k_fuse_unions<true>, g, blk, 0, s, fa)
-               : launch(k_fuse_unions<false>, g, blk, 0, s, fa);
+    const FuseLaunch f = fuse_unions_launch(p, oc_total, st.g_unions, out, fused, fused_mask);
+    e = p.reduction == DM_REDUCE_MAX ? launch(k_fuse_unions<true>, f.grid, f.block, 0, s, f.args)
+                                     : launch(k_fuse_unions<false>, f.grid, f.block, 0, s, f.args);
     if (e != hipSuccess) return e;
   }
 #ifdef DM_HOST_TIMING
@@ -717,8 +709,7 @@ hipError_t run_window_fused(const dm_params& p, const dm_frame* frames_host, con
   if (reinterpret_cast<uintptr_t>(out) % 16 != 0 || reinterpret_cast<uintptr_t>(mask) % 4 != 0)
     return hipErrorNotSupported;
   Staged st;
-  size_t slab_bytes = 0;
-  hipError_t e = stage_windows(p, frames_host, ws, ws_bytes, st, slab_bytes, s, nullptr);
+  hipError_t e = stage_windows(p, frames_host, ws, ws_bytes, st, s, nullptr);
   if (e == hipErrorOutOfMemory) {
     // The slabs of all frames do not fit the workspace (many parts of large windows): the fuse is
     // a max / min, so the frames go through in two halves, the second one folding into the map
@@ -742,9 +733,8 @@ hipError_t run_window_fused(const dm_params& p, const dm_frame* frames_host, con
     return e;
   }
   if (e != hipSuccess) return e;
-  return window_pass(p, st, reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + st.geom_bytes),
-                     depth, value, valid, nullptr, nullptr,
-                     p.vc ? p.vc : p.dc, p.fill, p.reduction == DM_REDUCE_MAX ? kMax : kMin, slab_bytes, s, out,
+  return window_pass(p, st, st.slabs, depth, value, valid, nullptr, nullptr,
+                     p.vc ? p.vc : p.dc, p.fill, p.reduction == DM_REDUCE_MAX ? kMax : kMin, st.arena.rest(), s, out,
                      mask, accumulate);
 }
 

@@ -854,6 +854,20 @@ k_fuse_unions(FuseArgs a) {
   }
 }
 
+// Host: arguments and launch geometry of the batch fuse of a whole call (all B frames, `oc` channels).  The kernel
+// is named where it is launched: a translation unit's device code lists its template kernels by first use.
+struct FuseLaunch { FuseArgs args; dim3 grid, block; };
+inline FuseLaunch fuse_unions_launch(const dm_params& p, int oc, const Win16* unions, const float* maps,
+                                     float* fused, uint8_t* fused_mask) {
+  FuseLaunch f;
+  f.args.B = p.B; f.args.b0 = 0; f.args.accumulate = 0;
+  f.args.dc = oc; f.args.mh = p.mh; f.args.mw = p.mw; f.args.fill = p.fill;
+  f.args.unions = unions; f.args.maps = maps; f.args.fused = fused; f.args.fused_mask = fused_mask;
+  f.grid = dim3((unsigned)(((size_t)p.mh * p.mw / 4 + kUnionGroups - 1) / kUnionGroups), oc);
+  f.block = dim3(kUnionGroups * kUnionLanes);
+  return f;
+}
+
 // Direct batch fuse from the slabs (dm_orth_project_fused_f32): fused[c] =
 // max/min over every (frame, part) window covering c of its slab value -- the
 // per-frame maps are never materialised.  Same block shape as k_fuse_unions; the
